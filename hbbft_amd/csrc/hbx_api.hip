@@ -116,6 +116,8 @@ struct hbx_ctx {
   dbuf coin_use;      // hbx_combine_signatures_d: the verified shares masked by the caller's subset
   // SyncKeyGen commitment checks (hbx_bivar_rows / hbx_bivar_check_acks)
   dbuf bv_commit48, bv_C, bv_cst, bv_rows, bv_rows48, bv_pst, bv_ackp, bv_acky, bv_vals, bv_out;
+  // SyncKeyGen SecretKey::decrypt (hbx_sk_decrypt): the key's limbs, plaintexts, HBX_CT_* per ciphertext
+  dbuf kg_sk, kg_out, kg_st;
   // opt-in kernel timing: event pairs per timed kernel (hbx_set_timing / hbx_kernel_time)
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> tev[HBX_K_COUNT];
@@ -566,7 +568,8 @@ int hbx_ctx_destroy(hbx_ctx* c) {
                   &c->coin_out96, &c->dec_st, &c->own_sk, &c->own_S, &c->own_part, &c->lines_d,
                   &c->vs_pk, &c->vs_lines_d, &c->coin_lines_d, &c->vs_blob, &c->vs_off, &c->vs_H, &c->vs_lines, &c->vs_scratch, &c->vs_sig96,
                   &c->vs_sig, &c->vs_sig_st, &c->vs_status, &c->fe1slot, &c->fb_lanes, &c->fb_coin, &c->hs[0], &c->hs[1], &c->hs[2], &c->hs[3], &c->hs[4], &c->hs[5], &c->coin_use, &c->bv_commit48, &c->bv_C, &c->bv_cst, &c->bv_rows,
-                  &c->bv_rows48, &c->bv_pst, &c->bv_ackp, &c->bv_acky, &c->bv_vals, &c->bv_out};
+                  &c->bv_rows48, &c->bv_pst, &c->bv_ackp, &c->bv_acky, &c->bv_vals, &c->bv_out,
+                  &c->kg_sk, &c->kg_out, &c->kg_st};
   for (dbuf* b : bufs) b->release();
   (void)hipEventDestroy(c->ev_last);
   if (c->coin_ready_ev) (void)hipEventDestroy(c->coin_ready_ev);
@@ -2015,6 +2018,264 @@ int hbx_decrypt_shares(hbx_ctx* c, const uint8_t* sk32, uint32_t n, const uint8_
   }
   cleanup();
   return ok ? HBX_OK : fail(c, HBX_E_DEVICE, "hbx_decrypt_shares: device error");
+}
+
+// ---- SyncKeyGen (src/sync_key_gen.rs) beyond the commitment checks -----------------------------
+namespace {
+// device buffer of one call
+struct kg_tmp : dbuf {
+  ~kg_tmp() { release(); }
+};
+// Ciphertexts per Ciphertext::verify pass of hbx_sk_decrypt.  The prepared-ciphertext state is about
+// 100 KiB per ciphertext (two sets of 2 x 68 Miller lines and their scratch), so 1024 bound it near
+// 100 MiB however many ciphertexts a call brings (N^2 = 65,536 at N = 256).  A larger chunk would not
+// run faster: the wide check gives a ciphertext-only job a whole 128-thread block (one 16-lane group
+// of its eight busy) and 45 KiB of LDS, so about 768 blocks are resident at a time.
+constexpr uint32_t SK_DECRYPT_CHUNK = 1024;
+
+void be32_to_limbs(const uint8_t* b, uint32_t* k8) {
+  for (int q = 0; q < 8; q++)
+    k8[q] = ((uint32_t)b[28 - 4 * q] << 24) | ((uint32_t)b[29 - 4 * q] << 16) | ((uint32_t)b[30 - 4 * q] << 8) | b[31 - 4 * q];
+}
+}  // namespace
+
+int hbx_encrypt_to(hbx_ctx* c, const uint8_t* pk48, const uint8_t* msg_blob, const uint64_t* msg_off, uint32_t count,
+                   const uint8_t* r32, uint8_t* u48, uint8_t* v_blob, uint8_t* w96) {
+  if (!c || !pk48 || !msg_off || !r32 || !u48 || !w96 || count == 0)
+    return fail(c, HBX_E_INVALID_ARG, "hbx_encrypt_to: bad args");
+  if (!scalars_canonical(r32, count)) return fail(c, HBX_E_INVALID_ARG, "hbx_encrypt_to: scalar >= r");
+  for (uint32_t j = 0; j < count; j++)
+    if (msg_off[j + 1] < msg_off[j]) return fail(c, HBX_E_INVALID_ARG, "hbx_encrypt_to: msg_off not monotone");
+  const uint64_t total = msg_off[count];
+  if (total && (!msg_blob || !v_blob)) return fail(c, HBX_E_INVALID_ARG, "hbx_encrypt_to: bad args");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = pick(c, c->stream);
+  stream_scope ss_{c, s};
+  kg_tmp dpkc, dpk, dst, dr, dm, doff, du, dv, dw;
+  if (!dpkc.ensure((size_t)count * 48) || !dpk.ensure((size_t)count * sizeof(g1a)) || !dst.ensure((size_t)count * 4) ||
+      !dr.ensure((size_t)count * 32) || !dm.ensure(total) || !doff.ensure((size_t)(count + 1) * 8) ||
+      !du.ensure((size_t)count * 48) || !dv.ensure(total) || !dw.ensure((size_t)count * 96))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_encrypt_to: out of device memory");
+  HIPCHK(c, hipMemcpyAsync(dpkc.p, pk48, (size_t)count * 48, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dr.p, r32, (size_t)count * 32, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(doff.p, msg_off, (size_t)(count + 1) * 8, hipMemcpyHostToDevice, s));
+  if (total) HIPCHK(c, hipMemcpyAsync(dm.p, msg_blob, total, hipMemcpyHostToDevice, s));
+  // decode = into_affine (curve + G1 membership), as a PublicKey deserialises
+  hipLaunchKernelGGL(k_decompress_shares, dim3((count + 255) / 256), dim3(256), 0, s, dpkc.as<uint8_t>(), (size_t)count,
+                     dpk.as<g1a>(), dst.as<int32_t>(), 1u, UINT32_MAX, nullptr);
+  HIPCHK(c, hipGetLastError());
+  std::vector<int32_t> st(count);
+  HIPCHK(c, hipMemcpyAsync(st.data(), dst.p, (size_t)count * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  for (uint32_t j = 0; j < count; j++)
+    if (st[j] != HBX_PT_OK)
+      return fail(c, HBX_E_INVALID_ARG, "hbx_encrypt_to: public key %u does not decode (status %d)", j, st[j]);
+  hipLaunchKernelGGL(k_encrypt_to, dim3((count + 63) / 64), dim3(64), 0, s, dpk.as<g1a>(), dr.as<uint8_t>(),
+                     dm.as<uint8_t>(), doff.as<uint64_t>(), count, du.as<uint8_t>(), dv.as<uint8_t>(), dw.as<uint8_t>(),
+                     c->digest);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(u48, du.p, (size_t)count * 48, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(w96, dw.p, (size_t)count * 96, hipMemcpyDeviceToHost, s));
+  if (total) HIPCHK(c, hipMemcpyAsync(v_blob, dv.p, total, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  return HBX_OK;
+}
+
+int hbx_sk_decrypt(hbx_ctx* c, const uint8_t* sk32, const uint8_t* u48, const uint8_t* v_blob, const uint64_t* v_off,
+                   const uint8_t* w96, uint32_t count, uint8_t* out_blob, uint8_t* status) {
+  if (!c || !sk32 || !u48 || !v_off || !w96 || !status || count == 0)
+    return fail(c, HBX_E_INVALID_ARG, "hbx_sk_decrypt: bad args");
+  if (!scalars_canonical(sk32, 1)) return fail(c, HBX_E_INVALID_ARG, "hbx_sk_decrypt: scalar >= r");
+  uint64_t maxv = 0;
+  for (uint32_t j = 0; j < count; j++) {
+    if (v_off[j + 1] < v_off[j]) return fail(c, HBX_E_INVALID_ARG, "hbx_sk_decrypt: v_off not monotone");
+    maxv = std::max<uint64_t>(maxv, v_off[j + 1] - v_off[j]);
+  }
+  const uint64_t total = v_off[count];
+  if (total && (!v_blob || !out_blob)) return fail(c, HBX_E_INVALID_ARG, "hbx_sk_decrypt: bad args");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = pick(c, c->stream);
+  stream_scope ss_{c, s};
+  if (!c->u_comp_own.ensure((size_t)count * 48) || !c->w_comp_own.ensure((size_t)count * 96) ||
+      !c->v_off_own.ensure((size_t)(count + 1) * 8) || !c->v_blob_own.ensure(total ? total : 16) ||
+      !c->kg_out.ensure(total ? total : 16) || !c->kg_st.ensure(count) || !c->kg_sk.ensure(32))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_sk_decrypt: out of device memory");
+  uint32_t limbs[8];
+  be32_to_limbs(sk32, limbs);
+  // an earlier call's kernels may still read kg_sk
+  HIPCHK(c, quiesce(c));
+  HIPCHK(c, hipMemcpy(c->kg_sk.p, limbs, 32, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpyAsync(c->u_comp_own.p, u48, (size_t)count * 48, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->w_comp_own.p, w96, (size_t)count * 96, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->v_off_own.p, v_off, (size_t)(count + 1) * 8, hipMemcpyHostToDevice, s));
+  if (total) HIPCHK(c, hipMemcpyAsync(c->v_blob_own.p, v_blob, total, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemsetAsync(c->kg_out.p, 0, total ? total : 16, s));
+  // Ciphertext::verify through the prepared-ciphertext path with its immediate checks, a chunk at a
+  // time.  `sk32` is the node's individual key, not its threshold share: own-share mode is off for
+  // these prepares and restored below; the epoch's prepared ciphertexts are void afterwards.
+  const uint32_t saved_me = c->own_me;
+  c->own_me = UINT32_MAX;
+  int rc = HBX_OK;
+  for (uint32_t j0 = 0; j0 < count && rc == HBX_OK; j0 += SK_DECRYPT_CHUNK) {
+    const uint32_t m = std::min(SK_DECRYPT_CHUNK, count - j0);
+    rc = prepare_impl(c, c->u_comp_own.as<uint8_t>() + (size_t)j0 * 48, c->v_blob_own.as<uint8_t>(),
+                      c->v_off_own.as<uint64_t>() + j0, c->w_comp_own.as<uint8_t>() + (size_t)j0 * 96, m, maxv,
+                      c->kg_st.as<uint8_t>() + j0, s, nullptr, 0);  // the chunk's HBX_CT_* land in kg_st
+    if (rc) break;
+    {
+      timed t_(c, HBX_K_SK_DECRYPT, s);
+      hipLaunchKernelGGL(k_sk_decrypt, dim3((m + 63) / 64), dim3(64), 0, s, c->U.as<g1a>(),
+                         c->kg_st.as<uint8_t>() + j0, c->kg_sk.as<uint32_t>(), c->v_blob_own.as<uint8_t>(),
+                         c->v_off_own.as<uint64_t>() + j0, m, c->kg_out.as<uint8_t>(), c->digest);
+    }
+    if (hipGetLastError() != hipSuccess) rc = fail(c, HBX_E_DEVICE, "hbx_sk_decrypt: device error");
+  }
+  c->own_me = saved_me;
+  c->own_ready = false;
+  c->p_ct = 0;
+  c->ct_known = false;
+  c->n_shares = 0;
+  c->verified_p = 0;
+  if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(status, c->kg_st.p, count, hipMemcpyDeviceToHost, s));
+  if (total) HIPCHK(c, hipMemcpyAsync(out_blob, c->kg_out.p, total, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  return HBX_OK;
+}
+
+int hbx_bivar_poly_rows(hbx_ctx* c, const uint8_t* coeff32, uint32_t t, uint32_t n, uint8_t* rows32) {
+  if (!c || !coeff32 || !rows32 || n == 0 || t > 4095) return fail(c, HBX_E_INVALID_ARG, "hbx_bivar_poly_rows: bad args");
+  const size_t M = (size_t)(t + 1) * (t + 2) / 2, lanes = (size_t)n * (t + 1);
+  if (lanes > (size_t)1 << 30) return fail(c, HBX_E_INVALID_ARG, "hbx_bivar_poly_rows: n (t + 1) too large");
+  if (!scalars_canonical(coeff32, M)) return fail(c, HBX_E_INVALID_ARG, "hbx_bivar_poly_rows: scalar >= r");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = pick(c, c->stream);
+  stream_scope ss_{c, s};
+  kg_tmp dc, dout;
+  if (!dc.ensure(M * 32) || !dout.ensure(lanes * 32))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_bivar_poly_rows: out of device memory");
+  HIPCHK(c, hipMemcpyAsync(dc.p, coeff32, M * 32, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_bivar_poly_rows, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, s, dc.as<uint8_t>(), t, n,
+                     dout.as<uint8_t>());
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(rows32, dout.p, lanes * 32, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  return HBX_OK;
+}
+
+int hbx_fr_poly_eval(hbx_ctx* c, const uint8_t* coeff32, uint32_t p, uint32_t t, uint32_t n, uint8_t* out32) {
+  if (!c || !coeff32 || !out32 || p == 0 || n == 0 || t > 4095)
+    return fail(c, HBX_E_INVALID_ARG, "hbx_fr_poly_eval: bad args");
+  const size_t nc = (size_t)p * (t + 1), lanes = (size_t)p * n;
+  if (lanes > (size_t)1 << 30 || nc > (size_t)1 << 30) return fail(c, HBX_E_INVALID_ARG, "hbx_fr_poly_eval: too large");
+  if (!scalars_canonical(coeff32, nc)) return fail(c, HBX_E_INVALID_ARG, "hbx_fr_poly_eval: scalar >= r");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = pick(c, c->stream);
+  stream_scope ss_{c, s};
+  kg_tmp dc, dout;
+  if (!dc.ensure(nc * 32) || !dout.ensure(lanes * 32))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_fr_poly_eval: out of device memory");
+  HIPCHK(c, hipMemcpyAsync(dc.p, coeff32, nc * 32, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_fr_poly_eval, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, s, dc.as<uint8_t>(), p, t, n,
+                     dout.as<uint8_t>());
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out32, dout.p, lanes * 32, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  return HBX_OK;
+}
+
+int hbx_keygen_generate(hbx_ctx* c, const uint8_t* commit48, uint32_t p, uint32_t t, const uint8_t* complete,
+                        const uint32_t* val_cnt, const uint64_t* val_y, const uint8_t* vals32, uint8_t* pk_commit48,
+                        uint8_t* sk32_out, uint8_t* status) {
+  if (!c || !commit48 || !complete || !pk_commit48 || !status || p == 0 || t > 4095)
+    return fail(c, HBX_E_INVALID_ARG, "hbx_keygen_generate: bad args");
+  if (sk32_out && (!val_cnt || !val_y || !vals32)) return fail(c, HBX_E_INVALID_ARG, "hbx_keygen_generate: null values");
+  const size_t M = (size_t)(t + 1) * (t + 2) / 2, nv = (size_t)p * (t + 1);
+  if (sk32_out) {
+    for (uint32_t q = 0; q < p; q++) {
+      if (!complete[q]) continue;
+      if (val_cnt[q] > t + 1) return fail(c, HBX_E_INVALID_ARG, "hbx_keygen_generate: part %u has %u > t + 1 values", q, val_cnt[q]);
+      const uint64_t* y = val_y + (size_t)q * (t + 1);
+      if (!scalars_canonical(vals32 + (size_t)q * (t + 1) * 32, val_cnt[q]))
+        return fail(c, HBX_E_INVALID_ARG, "hbx_keygen_generate: value >= r in part %u", q);
+      for (uint32_t a = 0; a < val_cnt[q]; a++)
+        for (uint32_t b = a + 1; b < val_cnt[q]; b++)
+          if (y[a] == y[b]) return fail(c, HBX_E_DUPLICATE_ENTRY, "hbx_keygen_generate: part %u repeats y = %llu", q, (unsigned long long)y[a]);
+    }
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = pick(c, c->stream);
+  stream_scope ss_{c, s};
+  kg_tmp dcomp, dcnt, dy, dv, dpkc, dpart, dsk;
+  if (!c->bv_commit48.ensure(p * M * 48) || !c->bv_C.ensure(p * M * sizeof(g1a)) || !c->bv_cst.ensure(p * M * 4) ||
+      !dcomp.ensure(p) || !dpkc.ensure((size_t)(t + 1) * 48) ||
+      (sk32_out && (!dcnt.ensure((size_t)p * 4) || !dy.ensure(nv * 8) || !dv.ensure(nv * 32) ||
+                    !dpart.ensure((size_t)p * sizeof(fr)) || !dsk.ensure(32))))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_keygen_generate: out of device memory");
+  HIPCHK(c, hipMemcpyAsync(c->bv_commit48.p, commit48, p * M * 48, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dcomp.p, complete, p, hipMemcpyHostToDevice, s));
+  if (sk32_out) {
+    HIPCHK(c, hipMemcpyAsync(dcnt.p, val_cnt, (size_t)p * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(dy.p, val_y, nv * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(dv.p, vals32, nv * 32, hipMemcpyHostToDevice, s));
+  }
+  // decode = into_affine (curve + G1 membership), as a Part's commitment deserialises
+  hipLaunchKernelGGL(k_decompress_shares, dim3((unsigned)((p * M + 255) / 256)), dim3(256), 0, s,
+                     c->bv_commit48.as<uint8_t>(), p * M, c->bv_C.as<g1a>(), c->bv_cst.as<int32_t>(), 1u, UINT32_MAX, nullptr);
+  HIPCHK(c, hipGetLastError());
+  std::vector<int32_t> cst(p * M);
+  HIPCHK(c, hipMemcpyAsync(cst.data(), c->bv_cst.p, p * M * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  bool bad = false;
+  for (uint32_t q = 0; q < p; q++) {
+    status[q] = complete[q] ? HBX_SHARE_VALID : HBX_SHARE_ABSENT;
+    for (size_t m = 0; complete[q] && m < M; m++) {
+      const int32_t st = cst[q * M + m];
+      if (st != HBX_PT_OK && st != HBX_PT_INFINITY) status[q] = HBX_SHARE_UNDECODABLE;
+    }
+    bad = bad || status[q] == HBX_SHARE_UNDECODABLE;
+  }
+  if (bad) return fail(c, HBX_E_INVALID_ARG, "hbx_keygen_generate: a complete part's commitment does not decode");
+  const uint32_t lanes = t + 1 + (sk32_out ? p : 0);
+  hipLaunchKernelGGL(k_keygen_generate, dim3((lanes + 63) / 64), dim3(64), 0, s, c->bv_C.as<g1a>(), p, t,
+                     dcomp.as<uint8_t>(), dcnt.as<uint32_t>(), dy.as<uint64_t>(), dv.as<uint8_t>(), dpkc.as<uint8_t>(),
+                     sk32_out ? dpart.as<fr>() : nullptr);
+  HIPCHK(c, hipGetLastError());
+  if (sk32_out) {
+    hipLaunchKernelGGL(k_keygen_sum, dim3(1), dim3(64), 0, s, dpart.as<fr>(), p, dsk.as<uint8_t>());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(sk32_out, dsk.p, 32, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(c, hipMemcpyAsync(pk_commit48, dpkc.p, (size_t)(t + 1) * 48, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  return HBX_OK;
+}
+
+int hbx_pk_shares_from_commit(hbx_ctx* c, const uint8_t* pk_commit48, uint32_t t, uint32_t n, uint8_t* pk48) {
+  if (!c || !pk_commit48 || !pk48 || n == 0 || t > 4095)
+    return fail(c, HBX_E_INVALID_ARG, "hbx_pk_shares_from_commit: bad args");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = pick(c, c->stream);
+  stream_scope ss_{c, s};
+  kg_tmp dcc, dP, dst, dout;
+  if (!dcc.ensure((size_t)(t + 1) * 48) || !dP.ensure((size_t)(t + 1) * sizeof(g1a)) || !dst.ensure((size_t)(t + 1) * 4) ||
+      !dout.ensure((size_t)n * 48))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_pk_shares_from_commit: out of device memory");
+  HIPCHK(c, hipMemcpyAsync(dcc.p, pk_commit48, (size_t)(t + 1) * 48, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_decompress_shares, dim3((t + 1 + 255) / 256), dim3(256), 0, s, dcc.as<uint8_t>(), (size_t)(t + 1),
+                     dP.as<g1a>(), dst.as<int32_t>(), 1u, UINT32_MAX, nullptr);
+  HIPCHK(c, hipGetLastError());
+  std::vector<int32_t> st(t + 1);
+  HIPCHK(c, hipMemcpyAsync(st.data(), dst.p, (size_t)(t + 1) * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  for (uint32_t j = 0; j <= t; j++)
+    if (st[j] != HBX_PT_OK && st[j] != HBX_PT_INFINITY)
+      return fail(c, HBX_E_INVALID_ARG, "hbx_pk_shares_from_commit: point %u does not decode (status %d)", j, st[j]);
+  hipLaunchKernelGGL(k_pk_shares_from_commit, dim3((n + 63) / 64), dim3(64), 0, s, dP.as<g1a>(), t, n, dout.as<uint8_t>());
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(pk48, dout.p, (size_t)n * 48, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  return HBX_OK;
 }
 
 }  // extern "C"

@@ -24,6 +24,7 @@
 #include "g1d.hpp"
 #include "curve4.hpp"
 #include "wide.hpp"
+#include "keygen.hpp"
 
 // Split build (tools/build.py): the kernels compile in groups, one translation unit per group
 // (-DHBX_TU=1..10: epoch, share checks, producer, wide checks, coin, broadcast, two-lane share
@@ -1051,16 +1052,15 @@ __global__ void __launch_bounds__(64) k_decrypt_shares(const uint8_t* __restrict
 // PublicKey::encrypt (honey_badger.rs:116) with explicit randomness r_j (threshold_crypto draws
 // it from thread_rng):  U = g1 r, V = M xor hash_bytes(pk r, |M|), W = hash_g1_g2(U, V) r.
 // One lane per message.
-__global__ void __launch_bounds__(64) k_encrypt(const g1a* __restrict__ pk, const uint8_t* __restrict__ r32,
-                                                const uint8_t* __restrict__ msg, const uint64_t* __restrict__ off,
-                                                uint32_t p, uint8_t* __restrict__ u48, uint8_t* __restrict__ v,
-                                                uint8_t* __restrict__ w96, int digest) {
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= p) return;
+// Message j of an encrypt launch under the key `pk`.
+__device__ __forceinline__ void encrypt_lane(const g1a& pk, uint32_t j, const uint8_t* __restrict__ r32,
+                                             const uint8_t* __restrict__ msg, const uint64_t* __restrict__ off,
+                                             uint8_t* __restrict__ u48, uint8_t* __restrict__ v,
+                                             uint8_t* __restrict__ w96, int digest) {
   uint32_t k[8];
   fr_from_be32(r32 + (size_t)j * 32, k);
   const g1a u = g1_to_affine(g1_mul_scalar(g1_from_affine(g1_generator()), k));
-  const g1a g = g1_to_affine(g1_mul_scalar(g1_from_affine(pk[0]), k));
+  const g1a g = g1_to_affine(g1_mul_scalar(g1_from_affine(pk), k));
   uint8_t* uc = u48 + (size_t)j * 48;
   g1_compress(u, uc);
   uint8_t gc[48], d[32];
@@ -1072,6 +1072,24 @@ __global__ void __launch_bounds__(64) k_encrypt(const g1a* __restrict__ pk, cons
   for (uint64_t q = 0; q < len; q++) v[o + q] = msg[o + q] ^ (uint8_t)chacha_next_u32(rng);
   const g2j h = hash_g1_g2(uc, v + o, len, digest);
   g2_compress(g2_to_affine(g2_mul_bits(h, k, 256)), w96 + (size_t)j * 96);
+}
+__global__ void __launch_bounds__(64) k_encrypt(const g1a* __restrict__ pk, const uint8_t* __restrict__ r32,
+                                                const uint8_t* __restrict__ msg, const uint64_t* __restrict__ off,
+                                                uint32_t p, uint8_t* __restrict__ u48, uint8_t* __restrict__ v,
+                                                uint8_t* __restrict__ w96, int digest) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= p) return;
+  encrypt_lane(pk[0], j, r32, msg, off, u48, v, w96, digest);
+}
+// PublicKey::encrypt to a different key per message (sync_key_gen.rs:295 the rows of a Part, :345
+// the values of an Ack): message j under pk[j].
+__global__ void __launch_bounds__(64) k_encrypt_to(const g1a* __restrict__ pk, const uint8_t* __restrict__ r32,
+                                                   const uint8_t* __restrict__ msg, const uint64_t* __restrict__ off,
+                                                   uint32_t p, uint8_t* __restrict__ u48, uint8_t* __restrict__ v,
+                                                   uint8_t* __restrict__ w96, int digest) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= p) return;
+  encrypt_lane(pk[j], j, r32, msg, off, u48, v, w96, digest);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -1130,6 +1148,84 @@ __global__ void __launch_bounds__(64) k_bivar_check(const g1j* __restrict__ rows
   for (int j = (int)t; j >= 0; j--) acc = g1_add(g1j_mul_u64(acc, ack_y[k]), R[j]);
   const g1j rhs = g1_mul_scalar(g1_from_affine(g1_generator()), v);
   out[k] = g1j_eq(acc, rhs) ? HBX_SHARE_VALID : HBX_SHARE_INVALID;
+}
+
+// ----------------------------------------------------------------------------------------------
+// SyncKeyGen beyond the commitment checks (keygen.hpp): one lane per item, 64-thread blocks.
+// ----------------------------------------------------------------------------------------------
+// SecretKey::decrypt (sync_key_gen.rs:326, :444) of `count` ciphertexts that went through the
+// prepared-ciphertext path: lane j decrypts where ct_valid[j] == HBX_CT_VALID and leaves its
+// (zeroed) output alone otherwise.  sk8: the node's own SecretKey, 8 LE limbs.
+__global__ void __launch_bounds__(64) k_sk_decrypt(const g1a* __restrict__ U, const uint8_t* __restrict__ ct_valid,
+                                                   const uint32_t* __restrict__ sk8, const uint8_t* __restrict__ v,
+                                                   const uint64_t* __restrict__ off, uint32_t count,
+                                                   uint8_t* __restrict__ out, int digest) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= count) return;
+  if (ct_valid[j] != HBX_CT_VALID) return;
+  uint32_t k[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) k[i] = sk8[i];
+  const uint64_t o = off[j];
+  kg_sk_decrypt(U[j], k, v + o, off[j + 1] - o, out + o, digest);
+}
+// BivarPoly::row(x) for x = 1..n (sync_key_gen.rs:293): lane (x - 1, j) -> rows32[x - 1][j].
+__global__ void __launch_bounds__(64) k_bivar_poly_rows(const uint8_t* __restrict__ coeff32, uint32_t t, uint32_t n,
+                                                        uint8_t* __restrict__ rows32) {
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= (uint64_t)n * (t + 1)) return;
+  const uint32_t xi = (uint32_t)(k / (t + 1)), j = (uint32_t)(k % (t + 1));
+  kg_fr_store_be(kg_bivar_row_coeff(coeff32, t, (uint64_t)xi + 1, j), rows32 + k * 32);
+}
+// row.evaluate(idx + 1) (sync_key_gen.rs:341) for p polynomials of degree t at n points:
+// lane (q, idx) -> out32[q][idx].
+__global__ void __launch_bounds__(64) k_fr_poly_eval(const uint8_t* __restrict__ coeff32, uint32_t p, uint32_t t,
+                                                     uint32_t n, uint8_t* __restrict__ out32) {
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= (uint64_t)p * n) return;
+  const uint32_t q = (uint32_t)(k / n), idx = (uint32_t)(k % n);
+  kg_fr_store_be(kg_poly_eval(coeff32 + (size_t)q * (t + 1) * 32, t, (uint64_t)idx + 1), out32 + k * 32);
+}
+// SyncKeyGen::generate (sync_key_gen.rs:396-409) over p decoded commitments C[p][M]:
+//  lanes 0..t:        pk_commit[j] = sum over complete parts of C_q[coeff_pos(0, j)] (`commit.row(0)`)
+//  lanes t+1..t+p:    part q = lane - (t + 1): interpolate(values).evaluate(0) over its cnt[q] <= t + 1
+//                     points -> part_val[q] (plain limbs; 0 for a part that is not complete)
+// k_keygen_sum adds the parts into the secret key share.
+__global__ void __launch_bounds__(64) k_keygen_generate(const g1a* __restrict__ C, uint32_t p, uint32_t t,
+                                                        const uint8_t* __restrict__ complete,
+                                                        const uint32_t* __restrict__ cnt,
+                                                        const uint64_t* __restrict__ val_y,
+                                                        const uint8_t* __restrict__ vals32,
+                                                        uint8_t* __restrict__ pk_commit48, fr* __restrict__ part_val) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t M = (t + 1) * (t + 2) / 2;
+  if (k <= t) {
+    g1j acc = g1_identity();
+    for (uint32_t q = 0; q < p; q++)
+      if (complete[q]) acc = g1_add_mixed_i(acc, C[(size_t)q * M + kg_coeff_pos(0, k)]);
+    g1_compress(g1_to_affine(acc), pk_commit48 + (size_t)k * 48);
+    return;
+  }
+  const uint32_t q = k - (t + 1);
+  if (q >= p || !part_val) return;
+  bool dup = false;  // never set here: hbx_keygen_generate refuses a repeated y on the host before the launch
+  const uint32_t c = cnt[q] <= t + 1 ? cnt[q] : t + 1;
+  part_val[q] = complete[q] ? kg_lagrange0_sum(val_y + (size_t)q * (t + 1), vals32 + (size_t)q * (t + 1) * 32, c, dup)
+                            : kg_fr_zero();
+}
+__global__ void __launch_bounds__(64) k_keygen_sum(const fr* __restrict__ part_val, uint32_t p,
+                                                   uint8_t* __restrict__ sk32) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  fr acc = kg_fr_zero();
+  for (uint32_t q = 0; q < p; q++) acc = fr_add(acc, part_val[q]);
+  kg_fr_store_be(acc, sk32);
+}
+// PublicKeySet::public_key_share(i) = commit.evaluate(i + 1) (messaging.rs:251-254), compressed.
+__global__ void __launch_bounds__(64) k_pk_shares_from_commit(const g1a* __restrict__ P, uint32_t t, uint32_t n,
+                                                              uint8_t* __restrict__ pk48) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  g1_compress(g1_to_affine(kg_commit_eval(P, t, (uint64_t)i + 1)), pk48 + (size_t)i * 48);
 }
 #endif
 

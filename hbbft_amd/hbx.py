@@ -89,6 +89,12 @@ EXPORTS = (
     "hbx_merkle_validate",
     "hbx_broadcast_decode",
     "hbx_broadcast_decode_leaves",
+    "hbx_encrypt_to",
+    "hbx_sk_decrypt",
+    "hbx_bivar_poly_rows",
+    "hbx_fr_poly_eval",
+    "hbx_keygen_generate",
+    "hbx_pk_shares_from_commit",
 )
 
 DIGEST_SHA256 = 0
@@ -110,7 +116,7 @@ CT_UNDECODABLE = 3
 # kernel ids of hbx_kernel_time (include/hbx.h)
 KERNELS = {"prepare_ct": 0, "prepare_lines": 1, "ct_checks": 2, "verify_shares": 3, "combine": 4,
            "verify_sig": 5, "combine_sigs": 6, "rs_code": 7, "merkle_leaves": 8, "hash_nonces": 9,
-           "decode_sigs": 10}
+           "decode_sigs": 10, "sk_decrypt": 11}
 
 _lib = None
 
@@ -178,6 +184,14 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.hbx_public_keys.argtypes = [P, u8p, u32, u8p]
     lib.hbx_encrypt.argtypes = [P, u8p, u8p, u64p, u32, u8p, u8p, u8p, u8p]
     lib.hbx_decrypt_shares.argtypes = [P, u8p, u32, u8p, u32, u8p]
+    # SyncKeyGen end to end
+    lib.hbx_encrypt_to.argtypes = [P, u8p, u8p, u64p, u32, u8p, u8p, u8p, u8p]
+    lib.hbx_sk_decrypt.argtypes = [P, u8p, u8p, u8p, u64p, u8p, u32, u8p, u8p]
+    lib.hbx_bivar_poly_rows.argtypes = [P, u8p, u32, u32, u8p]
+    lib.hbx_fr_poly_eval.argtypes = [P, u8p, u32, u32, u32, u8p]
+    lib.hbx_keygen_generate.argtypes = [P, u8p, u32, u32, u8p, ctypes.POINTER(ctypes.c_uint32), u64p, u8p, u8p, u8p,
+                                        u8p]
+    lib.hbx_pk_shares_from_commit.argtypes = [P, u8p, u32, u32, u8p]
     lib.hbx_set_timing.argtypes = [P, ctypes.c_int]
     lib.hbx_kernel_time.argtypes = [P, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint32)]
     lib.hbx_set_digest.argtypes = [P, ctypes.c_int]
@@ -556,6 +570,105 @@ class Context:
                                                   pr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
                                                   yy.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), _u8(vals32),
                                                   len(pr), _u8(out)))
+        return out
+
+    # -- SyncKeyGen end to end (src/sync_key_gen.rs) ---------------------------------------------
+    def encrypt_to(self, pk48: np.ndarray, msgs: Sequence[bytes], r32: np.ndarray):
+        """PublicKey::encrypt of msgs[j] to pk48[j] with randomness r32[j] -> list of (u48, v, w96)."""
+        pk48 = np.ascontiguousarray(pk48, dtype=np.uint8)
+        r32 = np.ascontiguousarray(r32, dtype=np.uint8)
+        count = len(msgs)
+        if pk48.shape != (count, 48) or r32.shape != (count, 32):
+            raise ValueError("encrypt_to: pk48 must be [count, 48] and r32 [count, 32] for count messages")
+        off = np.zeros(count + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(m) for m in msgs])
+        mb = np.frombuffer(b"".join(msgs) or b"\0", dtype=np.uint8).copy()
+        vb = np.zeros_like(mb)
+        u = np.zeros((count, 48), dtype=np.uint8)
+        w = np.zeros((count, 96), dtype=np.uint8)
+        self._check(self.lib.hbx_encrypt_to(self.h, _u8(pk48), _u8(mb),
+                                            off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), count, _u8(r32),
+                                            _u8(u), _u8(vb), _u8(w)))
+        return [(u[j].tobytes(), vb[int(off[j]):int(off[j + 1])].tobytes(), w[j].tobytes()) for j in range(count)]
+
+    def sk_decrypt(self, sk32: bytes, cts):
+        """SecretKey::decrypt of cts = list of (u48, v, w96) under the individual key sk32 ->
+        (list of plaintext bytes, zeros where the status is not CT_VALID; HBX_CT_* uint8[count]).
+        Voids the prepared epoch ciphertexts."""
+        count = len(cts)
+        sk = np.frombuffer(bytes(sk32), dtype=np.uint8).copy()
+        if sk.size != 32:
+            raise ValueError("sk_decrypt: sk32 must be 32 bytes")
+        u = np.frombuffer(b"".join(c[0] for c in cts), dtype=np.uint8).copy()
+        w = np.frombuffer(b"".join(c[2] for c in cts), dtype=np.uint8).copy()
+        if u.size != 48 * count or w.size != 96 * count:
+            raise ValueError("sk_decrypt: every ciphertext is (48 bytes, bytes, 96 bytes)")
+        off = np.zeros(count + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(c[1]) for c in cts])
+        vb = np.frombuffer(b"".join(c[1] for c in cts) or b"\0", dtype=np.uint8).copy()
+        out = np.zeros_like(vb)
+        st = np.zeros(count, dtype=np.uint8)
+        self._check(self.lib.hbx_sk_decrypt(self.h, _u8(sk), _u8(u), _u8(vb),
+                                            off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), _u8(w), count,
+                                            _u8(out), _u8(st)))
+        return [out[int(off[j]):int(off[j + 1])].tobytes() for j in range(count)], st
+
+    def bivar_poly_rows(self, coeff32: np.ndarray, t: int, n: int) -> np.ndarray:
+        """BivarPoly::row(x), x = 1..n, of coeff32 uint8[(t+1)(t+2)/2, 32] -> uint8[n, t + 1, 32]."""
+        coeff32 = np.ascontiguousarray(coeff32, dtype=np.uint8)
+        if coeff32.shape != ((t + 1) * (t + 2) // 2, 32):
+            raise ValueError("bivar_poly_rows: coeff32 must be [(t + 1)(t + 2)/2, 32]")
+        out = np.zeros((n, t + 1, 32), dtype=np.uint8)
+        self._check(self.lib.hbx_bivar_poly_rows(self.h, _u8(coeff32), t, n, _u8(out)))
+        return out
+
+    def fr_poly_eval(self, coeff32: np.ndarray, n: int) -> np.ndarray:
+        """Poly::evaluate(x), x = 1..n, of p polynomials coeff32 uint8[p, t + 1, 32] -> uint8[p, n, 32]."""
+        coeff32 = np.ascontiguousarray(coeff32, dtype=np.uint8)
+        if coeff32.ndim != 3 or coeff32.shape[2] != 32:
+            raise ValueError("fr_poly_eval: coeff32 must be [p, t + 1, 32]")
+        p, t = coeff32.shape[0], coeff32.shape[1] - 1
+        out = np.zeros((p, n, 32), dtype=np.uint8)
+        self._check(self.lib.hbx_fr_poly_eval(self.h, _u8(coeff32), p, t, n, _u8(out)))
+        return out
+
+    def keygen_generate(self, commits: np.ndarray, t: int, complete, val_cnt=None, val_y=None, vals32=None):
+        """SyncKeyGen::generate over commits uint8[p, (t+1)(t+2)/2, 48]: (pk_commit uint8[t + 1, 48],
+        sk share bytes or None for an observer (val_cnt None), status uint8[p]).  On HbxError the
+        per-part status of the failed call is in ``self.keygen_status``."""
+        commits = np.ascontiguousarray(commits, dtype=np.uint8)
+        p = commits.shape[0]
+        if commits.shape != (p, (t + 1) * (t + 2) // 2, 48):
+            raise ValueError("keygen_generate: commits must be [p, (t + 1)(t + 2)/2, 48]")
+        comp = np.ascontiguousarray(complete, dtype=np.uint8)
+        if comp.shape != (p,):
+            raise ValueError("keygen_generate: complete must be [p]")
+        pkc = np.zeros((t + 1, 48), dtype=np.uint8)
+        st = np.zeros(p, dtype=np.uint8)
+        self.keygen_status = st
+        if val_cnt is None:
+            self._check(self.lib.hbx_keygen_generate(self.h, _u8(commits), p, t, _u8(comp), None, None, None, _u8(pkc),
+                                                     None, _u8(st)))
+            return pkc, None, st
+        cnt = np.ascontiguousarray(val_cnt, dtype=np.uint32)
+        yy = np.ascontiguousarray(val_y, dtype=np.uint64)
+        vv = np.ascontiguousarray(vals32, dtype=np.uint8)
+        if cnt.shape != (p,) or yy.shape != (p, t + 1) or vv.shape != (p, t + 1, 32):
+            raise ValueError("keygen_generate: val_cnt [p], val_y [p, t + 1], vals32 [p, t + 1, 32]")
+        sk = np.zeros(32, dtype=np.uint8)
+        self._check(self.lib.hbx_keygen_generate(self.h, _u8(commits), p, t, _u8(comp),
+                                                 cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                                 yy.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), _u8(vv), _u8(pkc),
+                                                 _u8(sk), _u8(st)))
+        return pkc, sk.tobytes(), st
+
+    def pk_shares_from_commit(self, pk_commit48: np.ndarray, n: int) -> np.ndarray:
+        """public_key_share(i) = commit.evaluate(i + 1), i < n, of pk_commit48 uint8[t + 1, 48] -> uint8[n, 48]."""
+        pkc = np.ascontiguousarray(pk_commit48, dtype=np.uint8)
+        if pkc.ndim != 2 or pkc.shape[1] != 48:
+            raise ValueError("pk_shares_from_commit: pk_commit48 must be [t + 1, 48]")
+        out = np.zeros((n, 48), dtype=np.uint8)
+        self._check(self.lib.hbx_pk_shares_from_commit(self.h, _u8(pkc), pkc.shape[0] - 1, n, _u8(out)))
         return out
 
     # -- broadcast (torch tensors as HBM buffers) ------------------------------------------------

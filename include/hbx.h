@@ -124,7 +124,8 @@ const char* hbx_build_id(void);
 #define HBX_K_MERKLE_LEAVES 8   /* SHA-256 leaf hashes */
 #define HBX_K_HASH_NONCES 9     /* coin nonce hash_g2 */
 #define HBX_K_DECODE_SIGS 10    /* coin signature-share decode (G2 decompression; the checks test G2 membership) */
-#define HBX_K_COUNT 11
+#define HBX_K_SK_DECRYPT 11   /* SecretKey::decrypt keystream after the chunked Ciphertext::verify (hbx_sk_decrypt) */
+#define HBX_K_COUNT 12
 int hbx_set_timing(hbx_ctx* ctx, int on);
 int hbx_kernel_time(hbx_ctx* ctx, int kernel, double* total_ms, uint32_t* launches);
 
@@ -365,6 +366,53 @@ int hbx_bivar_rows(hbx_ctx* ctx, const uint8_t* commit48, uint32_t p, uint32_t t
 int hbx_bivar_check_acks(hbx_ctx* ctx, const uint8_t* commit48, uint32_t p, uint32_t t, uint64_t x,
                          const uint32_t* ack_proposer, const uint64_t* ack_y, const uint8_t* vals32, uint32_t count,
                          uint8_t* status);
+
+/* ---------------------------------------------------------------------------------------------
+ * SyncKeyGen end to end (src/sync_key_gen.rs): what surrounds the two
+ * commitment checks above.  Host-pointer forms; scalars are canonical 32-byte big-endian Fr
+ * (HBX_E_INVALID_ARG otherwise).  Plaintext framing is the caller's: the engine sees byte strings
+ * and raw scalars (DESIGN.md "Key generation": threshold_crypto's serde framing is parity-unpinned).
+ * Commitments (`our_part.commitment()` :291, `row.commitment()` :334) are hbx_public_keys applied
+ * to the coefficients: g1 * 0 is the identity encoding (0xC0, 47 zero bytes).
+ *
+ * hbx_encrypt_to -- PublicKey::encrypt to a DIFFERENT key per message: the encrypted rows of a Part
+ *   (sync_key_gen.rs:295, `pk.encrypt(&bytes)` per node) and the encrypted values of an Ack (:345).
+ *   As hbx_encrypt with pk48[count][48]; a key that does not decode to a G1 point other than the
+ *   identity is HBX_E_INVALID_ARG.
+ * hbx_sk_decrypt -- SecretKey::decrypt of our row of a Part (:326) and of our value of an Ack
+ *   (:444): Ciphertext::verify, then V xor hash_bytes(sk U, |V|), under the node's individual secret
+ *   key sk32 (not its threshold share).  status[count] = HBX_CT_*; out_blob (at the v_off offsets)
+ *   holds the plaintext where the status is HBX_CT_VALID and zeros elsewhere (the reference returns
+ *   None there).  Ciphertext::verify runs through the prepared-ciphertext path in chunks; own-share
+ *   mode stays as it was, but the epoch's prepared ciphertexts are void afterwards, as after
+ *   hbx_set_digest (a share verification then returns HBX_E_NO_CIPHERTEXTS until the next prepare).
+ * hbx_bivar_poly_rows -- BivarPoly::row(x) for x = 1..n (:293 `our_part.row(i + 1)`) of the dealer's
+ *   polynomial coeff32[(t+1)(t+2)/2][32] in coeff_pos order: rows32[n][t + 1][32].
+ * hbx_fr_poly_eval -- Poly::evaluate (:341 `row.evaluate(idx + 1)`) of p polynomials
+ *   coeff32[p][t + 1][32] at x = 1..n: out32[p][n][32].
+ * hbx_keygen_generate -- SyncKeyGen::generate (:396-409) over p Parts' commitments
+ *   commit48[p][(t+1)(t+2)/2][48]: pk_commit48[t + 1][48] = sum over the parts with complete[q] != 0 of
+ *   commit_q.row(0) (:401), and sk32_out = sum over those parts of
+ *   Poly::interpolate(values_q).evaluate(0) (:404-407) over the part's val_cnt[q] <= t + 1 points
+ *   (val_y[q][k], vals32[q][k]) (y = sender index + 1; a part with no point adds 0, fewer than t + 1
+ *   points interpolate through what there is).  sk32_out NULL (an observer): val_* are not read.
+ *   status[p]: HBX_SHARE_VALID, HBX_SHARE_ABSENT for a part that is not complete (not examined),
+ *   HBX_SHARE_UNDECODABLE for a complete part whose commitment holds a non-G1 point -- the call then
+ *   returns HBX_E_INVALID_ARG without writing the other outputs (the reference cannot hold such a
+ *   Part).  A repeated y within a complete part is HBX_E_DUPLICATE_ENTRY.
+ * hbx_pk_shares_from_commit -- PublicKeySet::public_key_share(i) = commit.evaluate(i + 1)
+ *   (src/messaging.rs:251-254) for i < n: pk48[n][48], the input of hbx_set_pk_shares.
+ * ------------------------------------------------------------------------------------------- */
+int hbx_encrypt_to(hbx_ctx* ctx, const uint8_t* pk48, const uint8_t* msg_blob, const uint64_t* msg_off,
+                   uint32_t count, const uint8_t* r32, uint8_t* u48, uint8_t* v_blob, uint8_t* w96);
+int hbx_sk_decrypt(hbx_ctx* ctx, const uint8_t* sk32, const uint8_t* u48, const uint8_t* v_blob,
+                   const uint64_t* v_off, const uint8_t* w96, uint32_t count, uint8_t* out_blob, uint8_t* status);
+int hbx_bivar_poly_rows(hbx_ctx* ctx, const uint8_t* coeff32, uint32_t t, uint32_t n, uint8_t* rows32);
+int hbx_fr_poly_eval(hbx_ctx* ctx, const uint8_t* coeff32, uint32_t p, uint32_t t, uint32_t n, uint8_t* out32);
+int hbx_keygen_generate(hbx_ctx* ctx, const uint8_t* commit48, uint32_t p, uint32_t t, const uint8_t* complete,
+                        const uint32_t* val_cnt, const uint64_t* val_y, const uint8_t* vals32, uint8_t* pk_commit48,
+                        uint8_t* sk32_out, uint8_t* status);
+int hbx_pk_shares_from_commit(hbx_ctx* ctx, const uint8_t* pk_commit48, uint32_t t, uint32_t n, uint8_t* pk48);
 
 /* ---------------------------------------------------------------------------------------------
  * Broadcast: Reed-Solomon erasure coding and the Merkle tree over shards (SURVEY.md §8 rows

@@ -8,6 +8,7 @@
 #include "../../hbbft_amd/csrc/g2d.hpp"
 #include "../../hbbft_amd/csrc/g1d.hpp"
 #include "../../hbbft_amd/csrc/hash.hpp"
+#include "../../hbbft_amd/csrc/keygen.hpp"
 using namespace hbx;
 extern "C" {
 // canonical big-endian 48-byte operands
@@ -489,5 +490,42 @@ int hc_sqrt_d_cmp(const uint8_t* x48) {
     if (!fq_eq(fq_canon(y1.c0), fq_canon(y2.c0)) || !fq_eq(fq_canon(y1.c1), fq_canon(y2.c1))) return 0;
   }
   return 1;
+}
+}
+extern "C" {
+// keygen.hpp (SyncKeyGen): scalars are canonical 32-byte big-endian Fr.
+// sum_j c_j x^j over deg + 1 coefficients (k_fr_poly_eval's lane)
+void hc_fr_poly_eval(const uint8_t* coeff32, uint32_t deg, uint64_t x, uint8_t* out32) {
+  kg_fr_store_be(kg_poly_eval(coeff32, deg, x), out32);
+}
+// BivarPoly::row(x) over the coeff_pos storage: out32[t + 1][32] (k_bivar_poly_rows' lanes of one x)
+void hc_bivar_poly_row(const uint8_t* coeff32, uint32_t t, uint64_t x, uint8_t* out32) {
+  for (uint32_t j = 0; j <= t; j++) kg_fr_store_be(kg_bivar_row_coeff(coeff32, t, x, j), out32 + 32 * j);
+}
+// sum_k lambda_k(0) v_k over cnt points (k_keygen_generate's part lane): returns 1 on a repeated y
+int hc_lagrange0_sum(const uint64_t* y, const uint8_t* vals32, uint32_t cnt, uint8_t* out32) {
+  bool dup = false;
+  kg_fr_store_be(kg_lagrange0_sum(y, vals32, cnt, dup), out32);
+  return dup ? 1 : 0;
+}
+// commit.evaluate(x) over t + 1 compressed G1 points (k_pk_shares_from_commit's lane); -1 if one does not decode
+int hc_commit_eval(const uint8_t* commit48, uint32_t t, uint64_t x, uint8_t* out48) {
+  g1a P[16];
+  if (t >= 16) return -2;
+  for (uint32_t j = 0; j <= t; j++) {
+    const int st = g1_decompress(commit48 + 48 * j, P[j]);
+    if (st != HBX_PT_OK && st != HBX_PT_INFINITY) return -1;
+  }
+  g1_compress(g1_to_affine(kg_commit_eval(P, t, x)), out48);
+  return 0;
+}
+// SecretKey::decrypt's xor (k_sk_decrypt's lane, after Ciphertext::verify); -1 if U does not decode
+int hc_sk_decrypt(const uint8_t* sk32, const uint8_t* u48, const uint8_t* v, uint64_t len, int digest, uint8_t* out) {
+  g1a U;
+  if (g1_decompress(u48, U) != HBX_PT_OK) return -1;
+  fr sk;
+  if (!kg_fr_load_be(sk32, sk)) return -2;
+  kg_sk_decrypt(U, sk.l, v, len, out, digest);
+  return 0;
 }
 }
