@@ -90,6 +90,14 @@ struct hbx_ctx {
   dbuf S, S_status, fallback, valid, shares_own, present_own, gslot;
   dbuf fe1slot;  // one-lane checks: the final exponentiation's global slots F, T, G (fe1d.hpp)
   uint32_t force_fallback = 0;  // hbx_debug_force_fallback (tests only)
+  // batched share verification (hbx_set_batch_verify): the seed, the index of the next batched
+  // verification under it, and the p of the last verification if that one was batched (else 0);
+  // key terms T[n + 1], ciphertext terms C[p], the sums Asum (affine) / AJ (Jacobian) / A / B [p],
+  // per-column classes, verdicts, the per-share launch's ciphertext gate and the three counters
+  bool batch_on = false;
+  uint64_t batch_call = 0;
+  uint32_t batch_last_p = 0;
+  dbuf b_seed, b_AJ, b_T, b_C, b_Asum, b_A, b_B, b_cls0, b_cand, b_pass, b_zero, b_cls, b_ctok, b_stats;
   // u32 counters of the checks the fallback path decided: one for the one-lane decryption-share
   // checks, one for the two-lane coin checks (launches of the two kinds on different streams must
   // not mix their counts); fb_last names the counter of the last share-check launch of either kind,
@@ -219,8 +227,9 @@ static void pack_bits(const uint8_t* bytes, size_t n, uint8_t* bits) {
 static bool scalars_canonical(const uint8_t* s32, size_t count);
 
 // Pairing checks of jobs [q_first, q_last] of every proposer (q < n: shares, q == n: ciphertext).
+// `ct_ok`: the proposers to examine (c->ct_ok, or the batched verification's gate of it).
 static int launch_pair_checks(hbx_ctx* c, hipStream_t s, uint32_t n, uint32_t p, uint32_t q_first, uint32_t q_last,
-                              const uint8_t* d_present) {
+                              const uint8_t* d_present, const uint8_t* ct_ok) {
   if (!c->fallback.ensure((size_t)p * (n + 1)))
     return fail(c, HBX_E_OUT_OF_MEMORY, "out of device memory (fallback flags)");
   HIPCHK(c, hipMemsetAsync(c->fallback.p, 0, (size_t)p * (n + 1), s));
@@ -229,7 +238,7 @@ static int launch_pair_checks(hbx_ctx* c, hipStream_t s, uint32_t n, uint32_t p,
     timed t_(c, HBX_K_CT_CHECKS, s);
     hipLaunchKernelGGL(k_verify_wide, dim3((jobs + WG_GROUPS - 1) / WG_GROUPS, p), dim3(WG_THREADS), 0, s,
                        c->S.as<g1a>(), c->S_status.as<int32_t>(), d_present, c->pk_m.as<g1a>(), c->n_keys,
-                       c->U.as<g1a>(), c->G2pts.as<g2a>(), c->lines.as<line_block>(), c->ct_ok.as<uint8_t>(), n,
+                       c->U.as<g1a>(), c->G2pts.as<g2a>(), c->lines.as<line_block>(), ct_ok, n,
                        q_first, q_last, c->valid.as<uint8_t>(), c->ct_valid.as<uint8_t>(), c->fallback.as<uint8_t>());
   }
   HIPCHK(c, hipGetLastError());
@@ -237,6 +246,53 @@ static int launch_pair_checks(hbx_ctx* c, hipStream_t s, uint32_t n, uint32_t p,
   hipLaunchKernelGGL(k_pair_fallback, dim3((unsigned)((all + 63) / 64)), dim3(64), 0, s, c->fallback.as<uint8_t>(),
                      c->S.as<g1a>(), c->pk_m.as<g1a>(), c->U.as<g1a>(), c->G2pts.as<g2a>(), c->lines.as<line_block>(),
                      n, p, c->valid.as<uint8_t>(), c->ct_valid.as<uint8_t>());
+  HIPCHK(c, hipGetLastError());
+  return HBX_OK;
+}
+
+// Batched verification, up to the per-share launch: one block per column for the share sums beside
+// the key terms, then A_j and B_j, the p column equations on the six-lane check (the lowest latency per check:
+// about half the 16-lane wide executor's for 256 columns, DESIGN.md "Batched share verification"), then
+// per column its class, the counters and the ciphertext
+// gate b_ctok under which the per-share kernels skip the columns the equation decided.
+static int launch_batch_columns(hbx_ctx* c, hipStream_t s, const uint8_t* d_present, uint32_t n, uint32_t p, bool own,
+                                bool fold) {
+  if (!c->b_AJ.ensure((size_t)p * sizeof(g1j)) || !c->b_T.ensure((size_t)(n + 1) * sizeof(g1j)) ||
+      !c->b_C.ensure((size_t)p * sizeof(g1j)) || !c->b_Asum.ensure((size_t)p * sizeof(g1a)) ||
+      !c->b_A.ensure((size_t)p * sizeof(g1a)) || !c->b_B.ensure((size_t)p * sizeof(g1a)) || !c->b_cls0.ensure(p) ||
+      !c->b_cand.ensure(p) || !c->b_pass.ensure(p) || !c->b_zero.ensure((size_t)p * 4) ||
+      !c->b_cls.ensure(p) || !c->b_ctok.ensure(p) || !c->b_stats.ensure(12))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_verify_dec_shares_d: out of device memory (batch)");
+  HIPCHK(c, hipMemsetAsync(c->b_zero.p, 0, (size_t)p * 4, s));
+  HIPCHK(c, hipMemsetAsync(c->b_pass.p, 0, p, s));
+  HIPCHK(c, hipMemsetAsync(c->b_stats.p, 0, 12, s));
+  {
+    timed t_(c, HBX_K_BATCH_MSM, s);
+    // the key-side lanes (n + 1, and p ciphertext terms with `fold`) as extra blocks of the same launch
+    const uint32_t key_blocks = (n + 1 + (fold ? p : 0) + BATCH_THREADS - 1) / BATCH_THREADS;
+    hipLaunchKernelGGL(k_batch_msm, dim3(p + key_blocks), dim3(BATCH_THREADS), 0, s, c->S.as<g1a>(),
+                       c->S_status.as<int32_t>(), d_present, n, c->n_keys, own ? c->own_me : UINT32_MAX,
+                       c->b_seed.as<uint8_t>(), c->batch_call, p, c->pk_m.as<g1a>(), fold ? 1u : 0u, c->b_T.as<g1j>(),
+                       c->b_C.as<g1j>(), c->ct_ok.as<uint8_t>(), c->ct_known ? c->ct_valid.as<uint8_t>() : nullptr,
+                       c->U.as<g1a>(), c->G2pts.as<g2a>(), c->b_Asum.as<g1a>(), c->b_AJ.as<g1j>(),
+                       c->b_cls0.as<uint8_t>(), c->b_cand.as<uint8_t>());
+    hipLaunchKernelGGL(k_batch_fin, dim3(p), dim3(BATCH_THREADS), 0, s, c->S_status.as<int32_t>(), d_present, n,
+                       c->n_keys, own ? c->own_me : UINT32_MAX, c->b_T.as<g1j>(), c->b_C.as<g1j>(), fold ? 1u : 0u,
+                       c->b_cand.as<uint8_t>(), c->b_Asum.as<g1a>(), c->b_AJ.as<g1j>(), c->b_A.as<g1a>(),
+                       c->b_B.as<g1a>());
+  }
+  HIPCHK(c, hipGetLastError());
+  {
+    timed t_(c, HBX_K_BATCH_CHECK, s);
+    // "one share per proposer": S = A, every status decodable, the key of column j = B_j, the
+    // verdict byte in b_pass (1 = the equation holds); the identity cases are check2_g6d's
+    hipLaunchKernelGGL(k_verify_shares6, dim3(1, p), dim3(64), 0, s, c->b_A.as<g1a>(), c->b_zero.as<int32_t>(), nullptr,
+                       c->b_B.as<g1a>(), 1u, c->G2pts.as<g2a>(), c->lines_d.as<line_block_d>(), c->b_cand.as<uint8_t>(),
+                       1u, c->b_pass.as<uint8_t>(), UINT32_MAX, nullptr, 1u);
+    hipLaunchKernelGGL(k_batch_mask, dim3((p + 63) / 64), dim3(64), 0, s, c->b_cls0.as<uint8_t>(), c->b_pass.as<uint8_t>(),
+                       c->ct_ok.as<uint8_t>(), p, c->b_cls.as<uint8_t>(), c->b_ctok.as<uint8_t>(),
+                       c->b_stats.as<uint32_t>());
+  }
   HIPCHK(c, hipGetLastError());
   return HBX_OK;
 }
@@ -569,7 +625,8 @@ int hbx_ctx_destroy(hbx_ctx* c) {
                   &c->vs_pk, &c->vs_lines_d, &c->coin_lines_d, &c->vs_blob, &c->vs_off, &c->vs_H, &c->vs_lines, &c->vs_scratch, &c->vs_sig96,
                   &c->vs_sig, &c->vs_sig_st, &c->vs_status, &c->fe1slot, &c->fb_lanes, &c->fb_coin, &c->hs[0], &c->hs[1], &c->hs[2], &c->hs[3], &c->hs[4], &c->hs[5], &c->coin_use, &c->bv_commit48, &c->bv_C, &c->bv_cst, &c->bv_rows,
                   &c->bv_rows48, &c->bv_pst, &c->bv_ackp, &c->bv_acky, &c->bv_vals, &c->bv_out,
-                  &c->kg_sk, &c->kg_out, &c->kg_st};
+                  &c->kg_sk, &c->kg_out, &c->kg_st, &c->b_seed, &c->b_AJ, &c->b_T, &c->b_C, &c->b_Asum, &c->b_A, &c->b_B,
+                  &c->b_cls0, &c->b_cand, &c->b_pass, &c->b_zero, &c->b_cls, &c->b_ctok, &c->b_stats};
   for (dbuf* b : bufs) b->release();
   (void)hipEventDestroy(c->ev_last);
   if (c->coin_ready_ev) (void)hipEventDestroy(c->coin_ready_ev);
@@ -614,6 +671,52 @@ int64_t hbx_get_fallback_lanes(hbx_ctx* c) {
   uint32_t v = 0;
   HIPCHK(c, hipMemcpy(&v, c->fb_last->p, 4, hipMemcpyDeviceToHost));
   return v;
+}
+
+int hbx_set_batch_verify(hbx_ctx* c, const uint8_t* seed32) {
+  if (!c) return HBX_E_INVALID_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, quiesce(c));  // a verification enqueued earlier may still read the old seed
+  c->batch_call = 0;
+  c->batch_on = false;
+  if (!seed32) return HBX_OK;
+  if (!c->b_seed.ensure(32)) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_set_batch_verify: out of device memory");
+  HIPCHK(c, hipMemcpy(c->b_seed.p, seed32, 32, hipMemcpyHostToDevice));
+  c->batch_on = true;
+  return HBX_OK;
+}
+
+int hbx_get_batch_stats(hbx_ctx* c, uint32_t* cols_batched, uint32_t* cols_fallback, uint32_t* cols_skipped) {
+  if (!c) return HBX_E_INVALID_ARG;
+  uint32_t v[3] = {0, 0, 0};
+  if (c->batch_last_p) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, quiesce(c));
+    HIPCHK(c, hipMemcpy(v, c->b_stats.p, 12, hipMemcpyDeviceToHost));
+  }
+  if (cols_batched) *cols_batched = v[0];
+  if (cols_fallback) *cols_fallback = v[1];
+  if (cols_skipped) *cols_skipped = v[2];
+  return HBX_OK;
+}
+
+int hbx_get_batch_sums(hbx_ctx* c, uint8_t* a48, size_t count) {
+  if (!c || !a48) return fail(c, HBX_E_INVALID_ARG, "hbx_get_batch_sums: bad args");
+  if (c->batch_last_p == 0) return fail(c, HBX_E_NO_CIPHERTEXTS, "hbx_get_batch_sums: the last verification was not batched");
+  if (count != c->batch_last_p)
+    return fail(c, HBX_E_INVALID_ARG, "hbx_get_batch_sums: count %zu, expected %u", count, c->batch_last_p);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, quiesce(c));
+  dbuf out;
+  if (!out.ensure(count * 48)) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_get_batch_sums: out of device memory");
+  hipLaunchKernelGGL(k_batch_compress, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, c->stream, c->b_Asum.as<g1a>(),
+                     (uint32_t)count, out.as<uint8_t>());
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = hipMemcpy(a48, out.p, count * 48, hipMemcpyDeviceToHost);
+  out.release();
+  if (e != hipSuccess) return fail(c, HBX_E_DEVICE, "hbx_get_batch_sums: %s", hipGetErrorString(e));
+  return HBX_OK;
 }
 
 int hbx_set_combine_lanes(hbx_ctx* c, int lanes) {
@@ -782,7 +885,7 @@ static int prepare_impl(hbx_ctx* c, const uint8_t* d_u_comp, const uint8_t* d_v_
     // Ciphertext::verify now: one check per proposer (n = 0 share jobs, job 0 = the ciphertext)
     if (!c->S.ensure(sizeof(g1a)) || !c->S_status.ensure(4) || !c->valid.ensure(16))
       return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_prepare_ciphertexts_d: out of device memory");
-    int rc = launch_pair_checks(c, s, 0, p, 0, 0, nullptr);
+    int rc = launch_pair_checks(c, s, 0, p, 0, 0, nullptr, c->ct_ok.as<uint8_t>());
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(d_ct_valid, c->ct_valid.p, p, hipMemcpyDeviceToDevice, s));
     c->ct_known = true;
@@ -852,9 +955,18 @@ static int verify_impl(hbx_ctx* c, const uint8_t* d_shares, const uint8_t* d_pre
                        own ? c->own_S.as<g1a>() : nullptr);
     HIPCHK(c, hipGetLastError());
   }
+  // batched mode: the column equations first; the launches below then see only the columns that
+  // failed theirs (ctok), and k_batch_merge writes the others' statuses
+  const bool batch = c->batch_on;
+  const uint8_t* ctok = c->ct_ok.as<uint8_t>();
+  if (batch) {
+    int rc = launch_batch_columns(c, s, d_present, n, p, own, !c->ct_known && !own);
+    if (rc) return rc;
+    ctok = c->b_ctok.as<uint8_t>();
+  }
   // ciphertext checks (if prepare deferred them): latency-bound, p checks -> 16-lane groups
   if (!c->ct_known && !own) {
-    int rc = launch_pair_checks(c, s, n, p, n, n, d_present);
+    int rc = launch_pair_checks(c, s, n, p, n, n, d_present, ctok);
     if (rc) return rc;
     c->ct_known = true;
   }
@@ -888,26 +1000,26 @@ static int verify_impl(hbx_ctx* c, const uint8_t* d_shares, const uint8_t* d_pre
         return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_verify_dec_shares_d: out of device memory (slots)");
       hipLaunchKernelGGL(k_verify_shares2, dim3((n + 31) / 32, p), dim3(64), 0, s, c->S.as<g1a>(),
                          c->S_status.as<int32_t>(), d_present, c->pk_m.as<g1a>(), c->n_keys, c->G2pts.as<g2a>(),
-                         c->lines_d.as<line_block_d>(), c->ct_ok.as<uint8_t>(), n, c->valid.as<uint8_t>(),
+                         c->lines_d.as<line_block_d>(), ctok, n, c->valid.as<uint8_t>(),
                          own ? c->own_me : UINT32_MAX,
                          (own && !c->ct_known) ? c->ct_valid.as<uint8_t>() : nullptr, c->gslot.as<uint32_t>());
     }
     else if (lanes == 6)
       hipLaunchKernelGGL(k_verify_shares6, dim3((n + G6_PER_WAVE - 1) / G6_PER_WAVE, p), dim3(64), 0, s,
                          c->S.as<g1a>(), c->S_status.as<int32_t>(), d_present, c->pk_m.as<g1a>(), c->n_keys,
-                         c->G2pts.as<g2a>(), c->lines_d.as<line_block_d>(), c->ct_ok.as<uint8_t>(), n,
+                         c->G2pts.as<g2a>(), c->lines_d.as<line_block_d>(), ctok, n,
                          c->valid.as<uint8_t>(), own ? c->own_me : UINT32_MAX,
-                         (own && !c->ct_known) ? c->ct_valid.as<uint8_t>() : nullptr);
+                         (own && !c->ct_known) ? c->ct_valid.as<uint8_t>() : nullptr, 0u);
     else if (lanes == 3)
       hipLaunchKernelGGL(k_verify_shares3, dim3((n + G3_PER_WAVE - 1) / G3_PER_WAVE, p), dim3(64), 0, s,
                          c->S.as<g1a>(), c->S_status.as<int32_t>(), d_present, c->pk_m.as<g1a>(), c->n_keys,
-                         c->G2pts.as<g2a>(), c->lines_d.as<line_block_d>(), c->ct_ok.as<uint8_t>(), n,
+                         c->G2pts.as<g2a>(), c->lines_d.as<line_block_d>(), ctok, n,
                          c->valid.as<uint8_t>(), own ? c->own_me : UINT32_MAX,
                          (own && !c->ct_known) ? c->ct_valid.as<uint8_t>() : nullptr);
     else if (lanes == 7)  // the one-lane check as one kernel (final exponentiation through call frames)
       hipLaunchKernelGGL(k_verify_shares, dim3((n + 63) / 64, p), dim3(64), 0, s, c->S.as<g1a>(),
                          c->S_status.as<int32_t>(), d_present, c->pk_m.as<g1a>(), c->n_keys, c->G2pts.as<g2a>(),
-                         c->lines_d.as<line_block_d>(), c->ct_ok.as<uint8_t>(), n, c->valid.as<uint8_t>(),
+                         c->lines_d.as<line_block_d>(), ctok, n, c->valid.as<uint8_t>(),
                          own ? c->own_me : UINT32_MAX,
                          (own && !c->ct_known) ? c->ct_valid.as<uint8_t>() : nullptr, 0u, nullptr);
     else {
@@ -924,8 +1036,7 @@ static int verify_impl(hbx_ctx* c, const uint8_t* d_shares, const uint8_t* d_pre
       c->fb_last = &c->fb_lanes;
       hipLaunchKernelGGL(k_verify_shares_ml, grid, dim3(64), 0, s, c->S.as<g1a>(), c->S_status.as<int32_t>(),
                          d_present, c->pk_m.as<g1a>(), c->n_keys, c->G2pts.as<g2a>(), c->lines_d.as<line_block_d>(),
-                         c->ct_ok.as<uint8_t>(), n, c->valid.as<uint8_t>(), me, gs);
-      const uint8_t* ctok = c->ct_ok.as<uint8_t>();
+                         ctok, n, c->valid.as<uint8_t>(), me, gs);
       uint8_t* vd = c->valid.as<uint8_t>();
       hipLaunchKernelGGL(k_fe1<0>, grid, dim3(64), 0, s, gs, n, vd, ctok, me, ctv, c->force_fallback);
       hipLaunchKernelGGL(k_fe1<1>, grid, dim3(64), 0, s, gs, n, vd, ctok, me, ctv, c->force_fallback);  // F1 + F2
@@ -939,6 +1050,14 @@ static int verify_impl(hbx_ctx* c, const uint8_t* d_shares, const uint8_t* d_pre
   }
   HIPCHK(c, hipGetLastError());
   c->ct_known = true;
+  if (batch) {
+    hipLaunchKernelGGL(k_batch_merge, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, c->b_cls.as<uint8_t>(),
+                       c->S_status.as<int32_t>(), d_present, n, p, c->n_keys, own ? c->own_me : UINT32_MAX,
+                       c->valid.as<uint8_t>(), c->ct_valid.as<uint8_t>());
+    HIPCHK(c, hipGetLastError());
+    c->batch_call++;
+  }
+  c->batch_last_p = batch ? p : 0;
   hipLaunchKernelGGL(k_gate_by_ct, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, c->valid.as<uint8_t>(),
                      c->ct_valid.as<uint8_t>(), n, p);
   HIPCHK(c, hipGetLastError());

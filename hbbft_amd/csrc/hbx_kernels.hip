@@ -25,6 +25,7 @@
 #include "curve4.hpp"
 #include "wide.hpp"
 #include "keygen.hpp"
+#include "batchd.hpp"
 
 // Split build (tools/build.py): the kernels compile in groups, one translation unit per group
 // (-DHBX_TU=1..10: epoch, share checks, producer, wide checks, coin, broadcast, two-lane share
@@ -992,7 +993,9 @@ __device__ __forceinline__ g1a g1_generator() {
 // k_verify_shares with SIX lanes per share (pairing3d.hpp check2_g6d: the two Miller loops on
 // two triplets side by side): 10 checks per wave.  For launches small enough that twice the
 // three-lane wave count still leaves at most one wave per SIMD (an epoch shard).  Same inputs,
-// outputs and own-share semantics.
+// outputs and own-share semantics.  The key of sender i in column j is pk[j * pk_col + i]: pk_col = 0 for
+// the senders' keys (one row for every proposer); the batched verification's column equations run
+// as "one share per proposer" with pk_col = 1, S = A_j and pk = B_j (k_batch_fin).
 __global__ void __launch_bounds__(64, 1) k_verify_shares6(const g1a* __restrict__ S, const int32_t* __restrict__ s_status,
                                                           const uint8_t* __restrict__ present,
                                                           const g1a* __restrict__ pk, uint32_t n_keys,
@@ -1000,7 +1003,7 @@ __global__ void __launch_bounds__(64, 1) k_verify_shares6(const g1a* __restrict_
                                                           const line_block_d* __restrict__ lines,
                                                           const uint8_t* __restrict__ ct_ok, uint32_t n,
                                                           uint8_t* __restrict__ valid, uint32_t me,
-                                                          uint8_t* __restrict__ ct_valid) {
+                                                          uint8_t* __restrict__ ct_valid, uint32_t pk_col) {
   const int lane = (int)(threadIdx.x & 63);
   if (lane >= 6 * G6_PER_WAVE) return;
   grp3 g;
@@ -1015,7 +1018,7 @@ __global__ void __launch_bounds__(64, 1) k_verify_shares6(const g1a* __restrict_
                                      ct_ok[j] != 0);
   bool v = false;
   if (res == HBX_SHARE_VALID) {
-    g1a npk = pk[i];
+    g1a npk = pk[(size_t)j * pk_col + i];
     npk.y = fq_neg(npk.y);
     v = check2_g6d(lines[j].h, S[idx], G2pts[2 * j].inf, lines[j].w, npk, G2pts[2 * j + 1].inf, second, g);
   }
@@ -1234,6 +1237,8 @@ __global__ void __launch_bounds__(64) k_pk_shares_from_commit(const g1a* __restr
 // proposer per 128-thread block sharing that proposer's prepared lines through LDS.
 //   job q <  n : share check  e(S_jq, H_j) e(-pk_q, W_j) == 1   (verify_decryption_share)
 //   job q == n : ct check     e(-U_j, H_j) e(g1, W_j) == 1      (Ciphertext::verify)
+// A block none of whose groups has a pairing to compute (undecodable or masked proposer, identity
+// cases) writes its results and returns before the schedule.
 // Jobs with a point at infinity are flagged for k_pair_fallback (the identity cases of check2).
 // ----------------------------------------------------------------------------------------------
 constexpr int WG_GROUPS = 8;
@@ -1258,7 +1263,6 @@ __global__ void __launch_bounds__(WG_THREADS) k_verify_wide(
   const int lane = tid % wide::G;
   const uint32_t j = blockIdx.y;
   const uint32_t q = q_first + blockIdx.x * WG_GROUPS + grp;
-  for (int t = tid; t < prog::NUM_K * wide::SLOT; t += WG_THREADS) lds[t] = prog::KCONST[t / wide::SLOT][t % wide::SLOT];
   const uint32_t gbase = (SH_SLOTS + grp * PRIV_SLOTS) * wide::SLOT;
   const uint32_t rbase = gbase + prog::MAX_SCRATCH * wide::SLOT;
   const uint32_t pbase = rbase + prog::NUM_REGIONS * 12 * wide::SLOT;
@@ -1290,6 +1294,15 @@ __global__ void __launch_bounds__(WG_THREADS) k_verify_wide(
     }
   }
   const bool needs_fallback = in_range && decodable && (PA.inf || PB.inf || qa_inf || qb_inf);
+  if (!__syncthreads_or(in_range && decodable && !needs_fallback)) {
+    if (lane == 0 && in_range) {
+      if (ct_job) ct_valid[j] = ct_ok[j] ? 0 : HBX_CT_UNDECODABLE;
+      else valid[(size_t)j * n + q] = 0;
+      fallback[(size_t)j * (n + 1) + q] = needs_fallback ? JOB_FALLBACK : 0;
+    }
+    return;
+  }
+  for (int t = tid; t < prog::NUM_K * wide::SLOT; t += WG_THREADS) lds[t] = prog::KCONST[t / wide::SLOT][t % wide::SLOT];
   // points: P[0..1] = P_A, P[2..3] = P_B  (any finite value for idle groups)
   if (lane < 4) {
     const g1a& pt = lane < 2 ? PA : PB;
@@ -1394,6 +1407,198 @@ __global__ void __launch_bounds__(64) k_pair_fallback(const uint8_t* __restrict_
   const bool v = check2(lines[j].h, PA, G2pts[2 * j].inf, lines[j].w, PB, G2pts[2 * j + 1].inf);
   if (q == n) ct_valid[j] = v ? 1 : 0;
   else valid[(size_t)j * n + q] = v ? 1 : 0;
+}
+#endif
+
+// ----------------------------------------------------------------------------------------------
+// Batched share verification (hbx_set_batch_verify; batchd.hpp, DESIGN.md "Batched share
+// verification"): one random-linear-combination equation per proposer column,
+//   e(A_j, H'_j) e(-B_j, W_j) == 1,  A_j = sum_i r_i S_ji [- r_ct U_j],  B_j = sum_i r_i [m] pk_i [- r_ct [m] g1],
+// decided by the six-lane check (k_verify_shares6 with pk_col = 1); only the columns whose equation fails go through
+// the per-share kernels, which see every other column's ciphertext as not decodable (ct_ok2) and
+// return before any pairing, and k_batch_merge then writes the passed columns' statuses.
+// ----------------------------------------------------------------------------------------------
+constexpr uint8_t BCOL_SKIPPED = 0;    // ciphertext undecodable or known invalid: not examined
+constexpr uint8_t BCOL_FALLBACK = 1;   // equation failed, or U / W / H is the identity: per-share checks
+constexpr uint8_t BCOL_BATCHED = 2;    // decided by the equation (k_batch_msm: a candidate for it)
+
+#if HBX_IN_TU(4)
+// The call's key-side terms, one lane each (the extra blocks of k_batch_msm's launch, so they run
+// beside the share terms): lanes i < n write T_i = r_i [m] pk_i (the identity for i >= n_keys), lane n
+// writes T_n = r_ct [m] g1, and with `fold` (Ciphertext::verify deferred into this verification) lanes
+// n + 1 + j write C_j = r_ct U_j.  The complete 12-limb routine: nothing is assumed of a key.
+__device__ void batch_key_lane(uint32_t gid, const uint8_t* __restrict__ seed32, uint64_t call_index,
+                               const g1a* __restrict__ pk_m, uint32_t n, uint32_t n_keys, const g1a* __restrict__ U,
+                               uint32_t p, uint32_t fold, g1j* __restrict__ T, g1j* __restrict__ C) {
+  if (gid > n + (fold ? p : 0u)) return;
+  uint32_t r4[4];
+  batch_coeff(seed32, call_index, gid < n ? gid : BATCH_CT_INDEX, r4);
+  if (gid < n) {
+    T[gid] = gid < n_keys ? g1_mul_u128_w4(pk_m[gid], r4) : g1_identity();
+  } else if (gid == n) {
+    g1a g;
+    g.x = fq_from_const(G1_MGEN_X);
+    g.y = fq_from_const(G1_MGEN_Y);
+    g.inf = false;
+    T[n] = fold ? g1_mul_u128_w4(g, r4) : g1_identity();
+  } else {
+    C[gid - n - 1] = g1_mul_u128_w4(U[gid - n - 1], r4);
+  }
+}
+
+__device__ __forceinline__ g1j g1j_shfl_down_b(const g1j& a, int off) {
+  g1j r;
+#pragma unroll
+  for (int i = 0; i < 12; i++) {
+    r.x.l[i] = (uint32_t)__shfl_down((int)a.x.l[i], off);
+    r.y.l[i] = (uint32_t)__shfl_down((int)a.y.l[i], off);
+    r.z.l[i] = (uint32_t)__shfl_down((int)a.z.l[i], off);
+  }
+  return r;
+}
+__device__ __forceinline__ g1a g1a_infinity() {
+  g1a r;
+  r.x = fq_zero();
+  r.y = fq_zero();
+  r.inf = true;
+  return r;
+}
+
+// Sum of one point per lane over the block with the complete addition (batchd.hpp): shuffles within a
+// wave, LDS across the four waves; the total is returned to thread 0 only.
+__device__ g1j batch_block_sum(g1j acc, g1j* part) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+#pragma unroll 1
+  for (int off = 32; off > 0; off >>= 1) {
+    const g1j o = g1j_shfl_down_b(acc, off);
+    if (lane < off) acc = g1_add(acc, o);
+  }
+  if (lane == 0) part[wv] = acc;
+  __syncthreads();
+  g1j sum = g1_identity();
+  if (tid == 0)
+    for (int q = 0; q < BATCH_THREADS / 64; q++) sum = g1_add(sum, part[q]);
+  return sum;
+}
+
+// Included senders of column j: present (or this node itself in own-share mode), a key known, the
+// share decoded.  A share that decoded to the identity is included: it adds its key term and no share
+// term, so its column's equation fails and the per-share path names it.
+__device__ __forceinline__ bool batch_included(int32_t st, bool present, bool known) {
+  return present && known && (st == HBX_PT_OK || st == HBX_PT_INFINITY);
+}
+
+// Blocks j < p: one block of BATCH_THREADS lanes per proposer column j, one lane per share (senders
+// past 256 in further rounds): the column's class, then r_i S_ji per lane (r_i derived in the lane)
+// and the block sum Asum_j = sum r_i S_ji, written affine (hbx_get_batch_sums) and Jacobian (AJ, for
+// k_batch_fin).  Blocks >= p: the key-side terms (batch_key_lane).
+// Two waves per SIMD: the few key-term blocks then run beside the p column blocks even when p
+// alone fills every compute unit (p = 256 on 256 CUs), instead of in a second round after them.
+__global__ void __launch_bounds__(BATCH_THREADS, 2) k_batch_msm(
+    const g1a* __restrict__ S, const int32_t* __restrict__ s_status, const uint8_t* __restrict__ present, uint32_t n,
+    uint32_t n_keys, uint32_t me, const uint8_t* __restrict__ seed32, uint64_t call_index, uint32_t p,
+    const g1a* __restrict__ pk_m, uint32_t fold, g1j* __restrict__ T, g1j* __restrict__ C,
+    const uint8_t* __restrict__ ct_ok, const uint8_t* __restrict__ ct_valid_known, const g1a* __restrict__ U,
+    const g2a* __restrict__ G2pts, g1a* __restrict__ Asum, g1j* __restrict__ AJ, uint8_t* __restrict__ cls0,
+    uint8_t* __restrict__ cand) {
+  __shared__ g1j part[BATCH_THREADS / 64];
+  const int tid = threadIdx.x;
+  if (blockIdx.x >= p) {
+    batch_key_lane((blockIdx.x - p) * BATCH_THREADS + (uint32_t)tid, seed32, call_index, pk_m, n, n_keys, U, p, fold, T,
+                   C);
+    return;
+  }
+  const uint32_t j = blockIdx.x;
+  uint8_t cls = BCOL_BATCHED;
+  if (!ct_ok[j] || (ct_valid_known && ct_valid_known[j] != HBX_CT_VALID)) cls = BCOL_SKIPPED;
+  else if (U[j].inf || G2pts[2 * j].inf || G2pts[2 * j + 1].inf) cls = BCOL_FALLBACK;
+  if (cls != BCOL_BATCHED) {  // block-uniform
+    if (tid == 0) {
+      Asum[j] = g1a_infinity();
+      cls0[j] = cls;
+      cand[j] = 0;
+    }
+    return;
+  }
+  g1j acc = g1_identity();
+  for (uint32_t i = (uint32_t)tid; i < n; i += BATCH_THREADS) {
+    const size_t idx = (size_t)j * n + i;
+    const int32_t st = s_status[idx];
+    if (st == HBX_PT_OK && batch_included(st, present == nullptr || present[idx] || i == me, i < n_keys)) {
+      uint32_t r4[4];
+      batch_coeff(seed32, call_index, i, r4);
+      acc = g1_add(acc, batch_term(S[idx], r4));
+    }
+  }
+  const g1j sum = batch_block_sum(acc, part);
+  if (tid == 0) {
+    AJ[j] = sum;
+    Asum[j] = g1_to_affine(sum);
+    cls0[j] = BCOL_BATCHED;
+    cand[j] = 1;
+  }
+}
+
+// The two G1 points of column j's equation, affine, once the key terms exist: thread 0 sums the
+// included senders' T_i over the block into B_j (minus T_n = r_ct [m] g1 with `fold`), and lane 0 of
+// wave 1 writes A_j = Asum_j (minus C_j = r_ct U_j with `fold`).
+__global__ void __launch_bounds__(BATCH_THREADS) k_batch_fin(
+    const int32_t* __restrict__ s_status, const uint8_t* __restrict__ present, uint32_t n, uint32_t n_keys, uint32_t me,
+    const g1j* __restrict__ T, const g1j* __restrict__ C, uint32_t fold, const uint8_t* __restrict__ cand,
+    const g1a* __restrict__ Asum, const g1j* __restrict__ AJ, g1a* __restrict__ A, g1a* __restrict__ B) {
+  __shared__ g1j part[BATCH_THREADS / 64];
+  const uint32_t j = blockIdx.x;
+  const int tid = threadIdx.x;
+  if (!cand[j]) {  // block-uniform
+    if (tid == 0) A[j] = B[j] = g1a_infinity();
+    return;
+  }
+  if (tid == 64) A[j] = fold ? g1_to_affine(g1_add(AJ[j], g1_neg(C[j]))) : Asum[j];
+  g1j acc = g1_identity();
+  for (uint32_t i = (uint32_t)tid; i < n; i += BATCH_THREADS) {
+    const size_t idx = (size_t)j * n + i;
+    if (batch_included(s_status[idx], present == nullptr || present[idx] || i == me, i < n_keys)) acc = g1_add(acc, T[i]);
+  }
+  const g1j sum = batch_block_sum(acc, part);
+  if (tid == 0) B[j] = g1_to_affine(fold ? g1_add(sum, g1_neg(T[n])) : sum);
+}
+
+// One lane per column after the column checks: the final class, the ciphertext gate of the
+// per-share launch (0 for a column the equation decided: its waves return at their precheck) and
+// the three counters of hbx_get_batch_stats (batched, fallback, skipped).
+__global__ void __launch_bounds__(64) k_batch_mask(const uint8_t* __restrict__ cls0, const uint8_t* __restrict__ pass,
+                                                   const uint8_t* __restrict__ ct_ok, uint32_t p,
+                                                   uint8_t* __restrict__ cls, uint8_t* __restrict__ ct_ok2,
+                                                   uint32_t* __restrict__ stats) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= p) return;
+  uint8_t c = cls0[j];
+  if (c == BCOL_BATCHED && pass[j] != 1) c = BCOL_FALLBACK;
+  cls[j] = c;
+  ct_ok2[j] = c == BCOL_BATCHED ? 0 : ct_ok[j];
+  atomicAdd(&stats[c == BCOL_BATCHED ? 0 : c == BCOL_FALLBACK ? 1 : 2], 1u);
+}
+
+// Statuses of the columns the equation decided, after the per-share launch wrote the others: every
+// included share is valid, the rest keep what the per-share precheck says of them; the column's
+// ciphertext is valid (checked eagerly, folded into the equation, or implied by the own share).
+__global__ void __launch_bounds__(256) k_batch_merge(const uint8_t* __restrict__ cls, const int32_t* __restrict__ s_status,
+                                                     const uint8_t* __restrict__ present, uint32_t n, uint32_t p,
+                                                     uint32_t n_keys, uint32_t me, uint8_t* __restrict__ valid,
+                                                     uint8_t* __restrict__ ct_valid) {
+  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= (size_t)n * p) return;
+  const uint32_t j = (uint32_t)(k / n), i = (uint32_t)(k % n);
+  if (cls[j] != BCOL_BATCHED) return;
+  valid[k] = share_precheck(s_status[k], present == nullptr || present[k] || i == me, i < n_keys, true);
+  if (i == 0) ct_valid[j] = HBX_CT_VALID;
+}
+
+__global__ void __launch_bounds__(64) k_batch_compress(const g1a* __restrict__ pts, uint32_t count,
+                                                       uint8_t* __restrict__ out48) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= count) return;
+  g1_compress(pts[j], out48 + (size_t)j * 48);
 }
 #endif
 

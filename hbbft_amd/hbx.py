@@ -95,6 +95,9 @@ EXPORTS = (
     "hbx_fr_poly_eval",
     "hbx_keygen_generate",
     "hbx_pk_shares_from_commit",
+    "hbx_set_batch_verify",
+    "hbx_get_batch_stats",
+    "hbx_get_batch_sums",
 )
 
 DIGEST_SHA256 = 0
@@ -116,7 +119,7 @@ CT_UNDECODABLE = 3
 # kernel ids of hbx_kernel_time (include/hbx.h)
 KERNELS = {"prepare_ct": 0, "prepare_lines": 1, "ct_checks": 2, "verify_shares": 3, "combine": 4,
            "verify_sig": 5, "combine_sigs": 6, "rs_code": 7, "merkle_leaves": 8, "hash_nonces": 9,
-           "decode_sigs": 10, "sk_decrypt": 11}
+           "decode_sigs": 10, "sk_decrypt": 11, "batch_msm": 12, "batch_check": 13}
 
 _lib = None
 
@@ -217,6 +220,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.hbx_broadcast_decode_leaves.argtypes = [P, P, P, P, P, u32, u32, u32, u32, P, ctypes.c_uint64, P, P]
     for name in ("hbx_get_share_status", "hbx_get_ct_status", "hbx_get_sig_share_status", "hbx_get_ct_hashes"):
         getattr(lib, name).argtypes = [P, u8p, ctypes.c_size_t]
+    # batched share verification: absent from a library built before it (tools/bench_batch_verify.py
+    # --lib times such a build in per-share mode)
+    if hasattr(lib, "hbx_set_batch_verify"):
+        lib.hbx_set_batch_verify.argtypes = [P, u8p]
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        lib.hbx_get_batch_stats.argtypes = [P, u32p, u32p, u32p]
+        lib.hbx_get_batch_sums.argtypes = [P, u8p, ctypes.c_size_t]
     _lib = lib
     return lib
 
@@ -304,6 +314,30 @@ class Context:
         if v < 0:
             self._check(v)
         return v
+
+    def set_batch_verify(self, seed: Optional[bytes]):
+        """hbx_set_batch_verify: decide each proposer's column of shares by one random-linear-combination
+        equation keyed by the 32-byte ``seed`` (which no sender may be able to predict); None = per-share
+        checks (default)."""
+        if seed is None:
+            self._check(self.lib.hbx_set_batch_verify(self.h, None))
+            return
+        if len(seed) != 32:
+            raise ValueError("batch seed must be 32 bytes")
+        buf = np.frombuffer(bytes(seed), dtype=np.uint8).copy()
+        self._check(self.lib.hbx_set_batch_verify(self.h, _u8(buf)))
+
+    def batch_stats(self):
+        """hbx_get_batch_stats: (cols_batched, cols_fallback, cols_skipped) of the last share verification."""
+        v = [ctypes.c_uint32() for _ in range(3)]
+        self._check(self.lib.hbx_get_batch_stats(self.h, *[ctypes.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    def batch_sums(self, p: int) -> np.ndarray:
+        """hbx_get_batch_sums (test hook): compressed A_j of the last batched verification -> uint8[p, 48]."""
+        out = np.zeros(p * 48, dtype=np.uint8)
+        self._check(self.lib.hbx_get_batch_sums(self.h, _u8(out), p))
+        return out.reshape(p, 48)
 
     def set_combine_lanes(self, lanes: int):
         """hbx_set_combine_lanes: 0 auto (default), 1 (a lane per Lagrange term) or 4 (a quad per term)."""

@@ -53,10 +53,13 @@ class EpochReplay:
     ``ctx`` must hold the era's key shares (``set_pk_shares``, n keys); ``sk_me`` is this node's
     32-byte secret key share, installed with ``set_own_share`` so the engine computes our own
     decryption shares (``decrypt_share_no_verify``, :403) and checks the ciphertexts through
-    them."""
+    them.  ``batch_seed`` (32 bytes no sender can predict, e.g. ``os.urandom(32)`` per epoch)
+    switches the context to batched share verification (``hbx_set_batch_verify``) for this replay's
+    verifications; the result is the same."""
 
-    def __init__(self, ctx, n: int, me: int, sk_me: bytes):
+    def __init__(self, ctx, n: int, me: int, sk_me: bytes, batch_seed: Optional[bytes] = None):
         self.ctx = ctx
+        self.batch_seed = None if batch_seed is None else bytes(batch_seed)
         self.n = n
         self.f = (n - 1) // 3  # NetworkInfo::num_faulty, messaging.rs:258
         # PublicKeySet::decrypt needs threshold + 1 = f + 1 shares (the key set's threshold is f)
@@ -105,6 +108,15 @@ class EpochReplay:
         return props, {pid: int(ct_status[j]) for j, pid in enumerate(props)}, status, layers
 
     def run(self, events) -> EpochResult:
+        if self.batch_seed is None:
+            return self._run(events)
+        self.ctx.set_batch_verify(self.batch_seed)
+        try:
+            return self._run(events)
+        finally:
+            self.ctx.set_batch_verify(None)
+
+    def _run(self, events) -> EpochResult:
         events = list(events)
         res = EpochResult(share_status=[None] * len(events))
         acs = [k for k, ev in enumerate(events) if ev[0] == "acs"]

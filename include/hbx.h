@@ -125,7 +125,9 @@ const char* hbx_build_id(void);
 #define HBX_K_HASH_NONCES 9     /* coin nonce hash_g2 */
 #define HBX_K_DECODE_SIGS 10    /* coin signature-share decode (G2 decompression; the checks test G2 membership) */
 #define HBX_K_SK_DECRYPT 11   /* SecretKey::decrypt keystream after the chunked Ciphertext::verify (hbx_sk_decrypt) */
-#define HBX_K_COUNT 12
+#define HBX_K_BATCH_MSM 12    /* batched verification: coefficients, key terms and the per-column sums A_j, B_j */
+#define HBX_K_BATCH_CHECK 13  /* batched verification: the p column equations and the column classes */
+#define HBX_K_COUNT 14
 int hbx_set_timing(hbx_ctx* ctx, int on);
 int hbx_kernel_time(hbx_ctx* ctx, int kernel, double* total_ms, uint32_t* launches);
 
@@ -171,6 +173,28 @@ int64_t hbx_get_fallback_lanes(hbx_ctx* ctx);
  * one-wave blocks (k_combine_q, t <= 128), 0 = by launch size (default: 4 when the quad blocks fit
  * in 1024 waves, else 1). */
 int hbx_set_combine_lanes(hbx_ctx* ctx, int lanes);
+/* Batched decryption-share verification by random linear combination (no reference counterpart;
+ * statuses identical except with probability <= 2^-128 per column, DESIGN.md "Batched share
+ * verification").  seed32 != NULL: hbx_verify_dec_shares[_d] and hbx_decrypt_epoch_d decide each
+ * proposer's column by one equation
+ *   e( sum_i r_i S_ji , H_j ) e( -sum_i r_i pk_i , W_j ) == 1
+ * over the included senders (present, known, share decoded) and run the per-share checks only for
+ * columns whose equation fails, which name the culprits as before.  seed32 == NULL: per-share
+ * checks (default).  Setting a seed resets the call index to 0.  Statuses written are those of the
+ * per-share path (HBX_SHARE_*, HBX_CT_*); a deferred Ciphertext::verify is folded into the equation.
+ * r_i = the little-endian integer of the first 16 bytes of SHA-256(seed32 || LE64(call_index) ||
+ * LE32(i)), i the sender index (0xFFFFFFFF: the ciphertext term), call_index the number of batched
+ * verifications since the seed was set; SHA-256 whatever hbx_set_digest says.  The seed MUST be
+ * unpredictable to every sender: with a known seed a sender can forge a column. */
+int hbx_set_batch_verify(hbx_ctx* ctx, const uint8_t* seed32);
+/* Columns of the last share verification: decided by the equation / sent to the per-share path
+ * (equation failed, or U_j, W_j or H_j is the identity) / not examined (ciphertext undecodable or
+ * already known invalid).  All 0 after a per-share verification.  Blocking. */
+int hbx_get_batch_stats(hbx_ctx* ctx, uint32_t* cols_batched, uint32_t* cols_fallback, uint32_t* cols_skipped);
+/* Test hook: A_j = sum_{i included} r_i S_ji of the last batched verification, compressed, p x 48
+ * (the identity encoding for an empty column and for one the equation was not evaluated for:
+ * skipped, or a ciphertext point is the identity).  count must equal p.  Blocking. */
+int hbx_get_batch_sums(hbx_ctx* ctx, uint8_t* a48, size_t count);
 int hbx_set_merkle_digest(hbx_ctx* ctx, int variant);
 
 /* ---------------------------------------------------------------------------------------------
