@@ -10,10 +10,12 @@
 //    ops; the 12-limb carry chain of fq_add / fq_sub is 36 ops plus the wait states gfx950
 //    inserts between carry-dependent instructions);
 //  * an Fq2 product is ONE fused column loop computing both Montgomery reductions: per column
-//    a0 b0 - a1 b1 and (a0 + a1)(b0 + b1) - a0 b0 - a1 b1 from three digit convolutions (Karatsuba)
-//    -- 3 x 196 + 2 x 196 = 980 v_mad instead of 3 x 392 = 1176.
+//    a0 b0 - a1 b1 and (a0 - a1)(b1 - b0) + a0 b0 + a1 b1 from three digit convolutions (Karatsuba
+//    on differences: one 64-bit subtraction per column) -- 3 x 196 + 2 x 196 = 980 v_mad instead of
+//    3 x 392 = 1176.
 // Bounds (all arithmetic on a column is exact modulo 2^64, so only the TRUE column value must fit
-// a signed 64-bit word -- intermediate wrap-around of the Karatsuba sum is harmless):
+// a signed 64-bit word -- intermediate wrap-around of the Karatsuba term is harmless: with operand
+// digits up to 2 x 2^28 the differences reach 4 x 2^28 and their convolution's column 14 x 2^60):
 //  * "normalised" (fqd_norm, every product output): digits 0..12 in [0, 2^28), digit 13 signed;
 //    value in (-p, 2p);
 //  * fqd_mul(a, b): max|a_i| max|b_i| <= 2^59;  fq2d_mul / fq2d_sqr: max|a_i| max|b_i| <= 2^58,
@@ -371,16 +373,21 @@ HBX_HD fq2d fq2d_relax(const fq2d& a) { return fq2d{fqd_relax(a.c0), fqd_relax(a
 // times xi = 1 + u
 HBX_HD fq2d fq2d_mul_xi(const fq2d& a) { return fq2d{fqd_sub(a.c0, a.c1), fqd_add(a.c0, a.c1)}; }
 
-// (a0 + a1 u)(b0 + b1 u): column k of  a0 b0 - a1 b1  and  (a0 + a1)(b0 + b1) - a0 b0 - a1 b1.
+// (a0 + a1 u)(b0 + b1 u): column k of  a0 b0 - a1 b1  and  a0 b1 + a1 b0, the cross term from
+// DIFFERENCES: (a0 - a1)(b1 - b0) + a0 b0 + a1 b1.  One 64-bit subtraction per column is left (each
+// is a v_sub_co / v_subb_co pair with a wait state behind it; a 64-bit addition is one instruction);
+// the sum form (a0 + a1)(b0 + b1) - a0 b0 - a1 b1 has three.  |a0 - a1|, |b1 - b0| <= 4 x 2^28 like
+// the sums; the difference convolution's column can leave int64 (14 x 2^60) and wraps, the true
+// columns (|a0 b0 - a1 b1|, |a0 b1 + a1 b0| <= 14 x 2 x 2^58 = 2^62.8) are the sum form's.
 // Operands: max|digit| products <= 2^58 (sums of two normalised values).  Output normalised.
 HBX_HD fq2d fq2d_mul(const fq2d& a, const fq2d& b) {
   HBX_DBOUND(a.c0, 2 * DN); HBX_DBOUND(a.c1, 2 * DN); HBX_DBOUND(b.c0, 2 * DN); HBX_DBOUND(b.c1, 2 * DN);
   HBX_COUNT_FQMUL(); HBX_COUNT_FQMUL(); HBX_COUNT_FQMUL();
-  int32_t sa[14], sb[14];
+  int32_t da[14], db[14];
 #pragma unroll
   for (int i = 0; i < 14; i++) {
-    sa[i] = a.c0.d[i] + a.c1.d[i];
-    sb[i] = b.c0.d[i] + b.c1.d[i];
+    da[i] = a.c0.d[i] - a.c1.d[i];
+    db[i] = b.c1.d[i] - b.c0.d[i];
   }
   fq2d r;
   fqd_redc2(
@@ -390,10 +397,10 @@ HBX_HD fq2d fq2d_mul(const fq2d& a, const fq2d& b) {
         for (int j = jlo; j <= jhi; j++) {
           t0 += (int64_t)a.c0.d[j] * (int64_t)b.c0.d[k - j];
           t1 += (int64_t)a.c1.d[j] * (int64_t)b.c1.d[k - j];
-          t2 += (int64_t)sa[j] * (int64_t)sb[k - j];
+          t2 += (int64_t)da[j] * (int64_t)db[k - j];
         }
         X = t0 - t1;
-        Y = t2 - t0 - t1;
+        Y = t2 + t0 + t1;
       },
       r.c0, r.c1);
   return r;
@@ -428,14 +435,17 @@ HBX_HD fq2d fq2d_sqr(const fq2d& a) {
 // Granger-Scott and Karabina cyclotomic squarings).  ONE column loop of six digit convolutions --
 // a^2, b^2 and e^2 = (a + b)^2 each as (x0 + x1)(x0 - x1) and x0 x1 -- combined per column into
 // the four output coordinates (c1 = e^2 - a^2 - b^2) and four Montgomery reductions: 6 + 4
-// reductions' worth of multiply-adds instead of three Fq2 squarings' 6 + 6.  a, b normalised;
-// every convolution column is below 14 x 2^57, an output's true column below 2^62.4 (the
+// reductions' worth of multiply-adds instead of three Fq2 squarings' 6 + 6.  a, b normalised.
+// The x0 x1 chains take a pre-doubled x0, so each chain multiplies digits of at most 2^29 (a sum,
+// a difference or a doubled digit) by digits of at most 2^28 (x0, x1 normalised and of one sign
+// each: of x0 + x1 and x0 - x1 one stays within 2^28): every convolution column is below
+// 14 x 2^57, and an output, which combines three of them, has a true column below 2^62.4 (the
 // combination is exact modulo 2^64, so only the true value must fit).  Normalised outputs.
 HBX_HD void fq4d_sqr_lazy(const fq2d& a, const fq2d& b, fq2d& c0, fq2d& c1) {
   HBX_DBOUND(a.c0, DN); HBX_DBOUND(a.c1, DN); HBX_DBOUND(b.c0, DN); HBX_DBOUND(b.c1, DN);
   HBX_COUNT_FQMUL(); HBX_COUNT_FQMUL(); HBX_COUNT_FQMUL(); HBX_COUNT_FQMUL(); HBX_COUNT_FQMUL();
   const fq2d e = fq2d_norm(fq2d_add(a, b));
-  int32_t sa[14], da[14], sb[14], db[14], se[14], de[14];
+  int32_t sa[14], da[14], sb[14], db[14], se[14], de[14], a2[14], b2[14], e2[14];
 #pragma unroll
   for (int i = 0; i < 14; i++) {
     sa[i] = a.c0.d[i] + a.c1.d[i];
@@ -444,25 +454,31 @@ HBX_HD void fq4d_sqr_lazy(const fq2d& a, const fq2d& b, fq2d& c0, fq2d& c1) {
     db[i] = b.c0.d[i] - b.c1.d[i];
     se[i] = e.c0.d[i] + e.c1.d[i];
     de[i] = e.c0.d[i] - e.c1.d[i];
+    a2[i] = a.c0.d[i] * 2;  // the imaginary parts' chains come out doubled: no 64-bit shifts per column
+    b2[i] = b.c0.d[i] * 2;
+    e2[i] = e.c0.d[i] * 2;
   }
   fqd r[4];
   fqd_redcn<4>(
       [&](int k, int jlo, int jhi, int64_t (&X)[4]) {
-        int64_t ar = 0, ai = 0, br = 0, bi = 0, er = 0, ei = 0;
+        int64_t ar = 0, ai2 = 0, br = 0, bi2 = 0, er = 0, ei2 = 0;
 #pragma unroll
         for (int j = jlo; j <= jhi; j++) {
           ar += (int64_t)sa[j] * (int64_t)da[k - j];
-          ai += (int64_t)a.c0.d[j] * (int64_t)a.c1.d[k - j];
+          ai2 += (int64_t)a2[j] * (int64_t)a.c1.d[k - j];
           br += (int64_t)sb[j] * (int64_t)db[k - j];
-          bi += (int64_t)b.c0.d[j] * (int64_t)b.c1.d[k - j];
+          bi2 += (int64_t)b2[j] * (int64_t)b.c1.d[k - j];
           er += (int64_t)se[j] * (int64_t)de[k - j];
-          ei += (int64_t)e.c0.d[j] * (int64_t)e.c1.d[k - j];
+          ei2 += (int64_t)e2[j] * (int64_t)e.c1.d[k - j];
         }
-        // a^2 = (ar, 2 ai), b^2 = (br, 2 bi), e^2 = (er, 2 ei); xi (x + y u) = (x - y) + (x + y) u
-        X[0] = ar + br - 2 * bi;
-        X[1] = 2 * ai + br + 2 * bi;
-        X[2] = er - ar - br;
-        X[3] = 2 * (ei - ai - bi);
+        // a^2 = (ar, ai2), b^2 = (br, bi2), e^2 = (er, ei2); xi (x + y u) = (x - y) + (x + y) u.
+        // Three 64-bit additions and three subtractions (a subtraction is two carry-linked
+        // instructions and a wait state, an addition one instruction).
+        const int64_t q = ar + br, p = ai2 + bi2;
+        X[0] = q - bi2;
+        X[1] = br + p;
+        X[2] = er - q;
+        X[3] = ei2 - p;
       },
       r);
   c0 = fq2d{r[0], r[1]};
