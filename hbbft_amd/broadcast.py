@@ -11,14 +11,15 @@ order, with the hashing and coding batched over the whole epoch on the GPU:
    per node;
 2. every proof the state machines would validate (Values from the proposer against our index,
    every Echo against its sender, :430, :451) goes into one ``hbx_merkle_validate_d`` call per
-   distinct value length; validation is deterministic, so doing it early changes no result;
+   distinct value length (``ragged=True``: one ``hbx_merkle_validate_ragged_d`` call for all of
+   them); validation is deterministic, so doing it early changes no result;
 3. the messages are replayed in arrival order through the reference's control flow with those
    bits standing in for ``validate_proof``; each time ``compute_output`` would decode, the
    attempt (root, Echo senders holding that root) is recorded instead.  A decode result only sets
    ``decided`` (and the output): sending Echo / Ready and every fault are independent of it, so
    the replay of everything else does not wait for decodes;
 4. the attempts are decoded in two waves with ``hbx_broadcast_decode_leaves_d`` (each wave one
-   call per shard length): first every instance's first attempt, then all remaining distinct
+   call per shard length; ``ragged=True``: one ``hbx_broadcast_decode_ragged_d`` call): first every instance's first attempt, then all remaining distinct
    attempts of the instances whose first decode failed -- a failed decode is retried with the
    Echo values held at each later trigger, exactly as ``compute_output`` does, and an attempt
    identical to a failed one is not decoded again.  The decode takes the present shards' leaf
@@ -105,6 +106,31 @@ def flatten_proofs(proofs, nodes) -> Tuple[np.ndarray, ...]:
     return vals, nh, sh, sides, depth, root, np.asarray(nodes, dtype=np.uint32)
 
 
+def flatten_proofs_ragged(proofs, nodes) -> Tuple[np.ndarray, ...]:
+    """Proofs of any value lengths -> (value blob, val_off uint64[P + 1], node_hash, sib_hash, sides,
+    depth, root, sender): the layout of hbx_merkle_validate_ragged_d."""
+    P = len(proofs)
+    val_off = np.zeros(P + 1, dtype=np.uint64)
+    val_off[1:] = np.cumsum([len(p["value"]) for p in proofs])
+    blob = np.frombuffer(b"".join(bytes(p["value"]) for p in proofs), dtype=np.uint8).copy()
+    nh = np.zeros((P, 17, 32), dtype=np.uint8)
+    sh = np.zeros((P, 16, 32), dtype=np.uint8)
+    sides = np.zeros(P, dtype=np.uint32)
+    depth = np.zeros(P, dtype=np.uint32)
+    root = np.zeros((P, 32), dtype=np.uint8)
+    for j, p in enumerate(proofs):
+        lem = p["lemma"]
+        depth[j] = len(lem) - 1
+        for lv, (h, sib) in enumerate(lem):
+            nh[j, lv] = np.frombuffer(bytes(h), dtype=np.uint8)
+            if sib is not None:
+                sh[j, lv] = np.frombuffer(bytes(sib[1]), dtype=np.uint8)
+                if sib[0] == "L":
+                    sides[j] |= np.uint32(1 << lv)
+        root[j] = np.frombuffer(bytes(p["root_hash"]), dtype=np.uint8)
+    return blob, val_off, nh, sh, sides, depth, root, np.asarray(nodes, dtype=np.uint32)
+
+
 def unflatten_proof(value: bytes, nh: np.ndarray, sh: np.ndarray, sides: int, depth: int, root: np.ndarray):
     lemma = []
     for lv in range(depth):
@@ -120,12 +146,15 @@ class GpuBroadcastEngine:
     """The three batched operations the replay needs, through ``hbx.Context`` (torch tensors are
     the HBM buffers; torch is plumbing only)."""
 
-    def __init__(self, ctx, merkle_variant: int = 0, stream=None):
+    def __init__(self, ctx, merkle_variant: int = 0, stream=None, ragged: bool = False):
+        """ragged: validate() and decode() make one engine call each (the ragged entry points,
+        per-instance shard lengths) instead of one per value / shard length."""
         import torch
 
         self.torch = torch
         self.ctx = ctx
         self.stream = stream
+        self.ragged = ragged
         ctx.set_merkle_digest(merkle_variant)
 
     def _dev(self, a):
@@ -161,8 +190,19 @@ class GpuBroadcastEngine:
                 for i in range(n)]
 
     def validate(self, proofs, nodes, n: int) -> np.ndarray:
-        """Broadcast::validate_proof(p, node) for each (p, node): one engine call per value length."""
+        """Broadcast::validate_proof(p, node) for each (p, node): one engine call per value length
+        (ragged: one call for all of them)."""
         torch = self.torch
+        if self.ragged:
+            if not proofs:
+                return np.zeros(0, dtype=bool)
+            blob, val_off, *arrs = flatten_proofs_ragged(proofs, nodes)
+            d_blob = self._dev(blob if blob.size else np.zeros(1, dtype=np.uint8))
+            d = [self._dev(a) for a in arrs]
+            valid = torch.zeros(len(proofs), dtype=torch.uint8, device=d_blob.device)
+            self.ctx.merkle_validate_ragged_d(d_blob, val_off, *d, n, valid, stream=self.stream)
+            torch.cuda.synchronize(d_blob.device)
+            return valid.cpu().numpy().astype(bool)
         out = np.zeros(len(proofs), dtype=bool)
         groups: Dict[int, List[int]] = {}
         for q, p in enumerate(proofs):
@@ -192,6 +232,9 @@ class GpuBroadcastEngine:
                 # the glued data has k * 0 < 4 bytes, so glue_shards returns None (broadcast.rs:697-707)
                 continue
             groups.setdefault(lens.pop(), []).append(q)
+        if self.ragged:
+            self._decode_ragged([q for _, idx in sorted(groups.items()) for q in idx], attempts, n, out)
+            return out
         for vlen, idx in sorted(groups.items()):
             L = vlen - 1  # the index byte is implied by the position (validate_proof checked it)
             inst = len(idx)
@@ -220,6 +263,44 @@ class GpuBroadcastEngine:
                 if st[r] == 0:
                     out[q] = ob[r, : int(ln[r])].tobytes()
         return out
+
+
+    def _decode_ragged(self, idx, attempts, n: int, out):
+        """All decodable attempts, whatever their shard lengths, in one hbx_broadcast_decode_ragged_d."""
+        if not idx:
+            return
+        torch = self.torch
+        k, m = coding_counts(n)
+        inst = len(idx)
+        lens = np.array([len(next(v for v in attempts[q][0] if v is not None)) - 1 for q in idx], dtype=np.uint32)
+        off, pitch, total = self.ctx.ragged_layout(lens, n)
+        buf = np.zeros(total, dtype=np.uint8)
+        present = np.zeros((inst, n), dtype=np.uint8)
+        leaf = np.zeros((inst, n, 32), dtype=np.uint8)
+        roots = np.zeros((inst, 32), dtype=np.uint8)
+        for r, q in enumerate(idx):
+            vals, digests, root = attempts[q]
+            rows = buf[int(off[r]): int(off[r]) + n * int(pitch[r])].reshape(n, int(pitch[r]))
+            for i, v in enumerate(vals):
+                if v is not None:
+                    rows[i, : lens[r]] = np.frombuffer(bytes(v), dtype=np.uint8, offset=1)
+                    present[r, i] = 1
+                    leaf[r, i] = np.frombuffer(bytes(digests[i]), dtype=np.uint8)
+            roots[r] = np.frombuffer(bytes(root), dtype=np.uint8)
+        room = (np.maximum(k * lens.astype(np.int64) - 4, 0) + 15) // 16 * 16
+        out_off = np.concatenate(([0], np.cumsum(room)[:-1])).astype(np.uint64)
+        d_buf = self._dev(buf)
+        dev = d_buf.device
+        d_out = torch.zeros(max(int(room.sum()), 16), dtype=torch.uint8, device=dev)
+        d_len = torch.zeros(inst, dtype=torch.int64, device=dev)
+        d_st = torch.zeros(inst, dtype=torch.int32, device=dev)
+        self.ctx.broadcast_decode_ragged_d(d_buf, off, lens, pitch, self._dev(present), self._dev(roots), k, m, d_out,
+                                           out_off, d_len, d_st, d_leaf_hash=self._dev(leaf), stream=self.stream)
+        torch.cuda.synchronize(dev)
+        st, ln, ob = d_st.cpu().numpy(), d_len.cpu().numpy(), d_out.cpu().numpy()
+        for r, q in enumerate(idx):
+            if st[r] == 0:
+                out[q] = ob[int(out_off[r]): int(out_off[r]) + int(ln[r])].tobytes()
 
 
 # ---------------------------------------------------------------------------------------------

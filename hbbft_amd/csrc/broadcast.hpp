@@ -5,6 +5,8 @@
 //
 // HBM layout: one instance = n shards of L bytes, contiguous ([inst][n][L]); leaf i of an
 // instance is the index byte i followed by shard i (broadcast.rs:373-377), never materialised.
+// The ragged kernels (*_rg) take instances of different L from one buffer: a descriptor per
+// instance (rg_desc: offset, length, row pitch) in place of {inst_stride, L}.
 // All of it is byte/integer work: the roofline is HBM bandwidth for RS (k reads + m writes per
 // column) and the integer VALU for SHA-256 (64 rounds per 64-byte block); no MFMA.
 #pragma once
@@ -46,6 +48,14 @@ struct rs_job {
   int32_t n_out;
   int32_t in_idx[RS_MAX_K];
   int32_t out_idx[RS_MAX_N];
+};
+
+// Ragged layout (include/hbx.h, the *_ragged_d calls): instance q of one byte buffer has its row
+// i at off + i * pitch and a shard length len <= pitch; off and pitch are multiples of 4.
+struct rg_desc {
+  uint64_t off;
+  uint32_t len;
+  uint32_t pitch;
 };
 
 // grid (ceil(L / (4 * 256)), inst); thread = 4 consecutive byte columns of one instance.
@@ -298,6 +308,113 @@ __host__ __device__ constexpr size_t rs_perm3_lds_bytes(uint32_t k, int ch) {
 #ifndef HBX_RS3_WPE
 #define HBX_RS3_WPE 1  // tuning: minimum waves per EU of the triple kernel (__launch_bounds__'s second bound)
 #endif
+// k_rs_code_perm3's coding of one block, with the row pitch apart from the row length: row r is the
+// Ld dwords at base + r * Pd.  The body of the ragged kernel below; the uniform kernel keeps its
+// own copy, because sharing this one moved its register allocation.
+template <int CH, int D>
+__device__ __forceinline__ void rs_perm3_block(uint32_t* base, uint32_t Ld, uint32_t Pd, uint32_t k, const rs_job* J,
+                                               const gf_ptab* tb) {
+  extern __shared__ uint4 rs_lds[];
+  const uint32_t nt = (k + 2) / 3;
+  const int no = ld_uniform(&J->n_out);
+  if (no == 0) return;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wave0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 64 * D;
+  bool ok[D];
+#pragma unroll
+  for (int j = 0; j < D; j++) ok[j] = wave0 + lane + 64 * j < Ld;
+  auto load_in = [&](uint32_t c, uint32_t* d) {
+    if (c < k) {
+      const uint32_t* src = base + (size_t)ld_uniform(&J->in_idx[c]) * Pd + wave0 + lane;
+#pragma unroll
+      for (int j = 0; j < D; j++) d[j] = ok[j] ? src[64 * j] : 0u;
+    } else {
+#pragma unroll
+      for (int j = 0; j < D; j++) d[j] = 0u;
+    }
+  };
+  auto tbyte = [](uint32_t w, int i) { return (w >> (8 * i)) & 0xffu; };
+  // passes of CH outputs spread over grid.z (host: ceil(expected outputs / CH)); more outputs
+  // than the grid covers loop here
+  for (int o0 = blockIdx.z * CH; o0 < no; o0 += gridDim.z * CH) {
+    __syncthreads();  // previous pass done with the tables
+    for (uint32_t e = threadIdx.x; e < nt * CH; e += blockDim.x) {
+      const uint32_t t = e / CH, o = e % CH;
+      gf_ptab g[3];
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        const uint32_t c = 3 * t + i;
+        g[i] = gf_ptab{};
+        if (c < k && o0 + (int)o < no) g[i] = tb[(size_t)(o0 + o) * k + c];
+      }
+      // T2 (w[4]) byte i = c * (i << 6): byte 1 = c * 0x40, byte 2 = c * 0x80
+      uint32_t m1[2] = {0, 0}, m2[2] = {0, 0};
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        const uint32_t v1 = tbyte(g[0].w[4], j & 3) ^ ((j & 4) ? tbyte(g[1].w[4], 1) : 0u);
+        const uint32_t v2 = ((j & 1) ? tbyte(g[1].w[4], 2) : 0u) ^ tbyte(g[2].w[4], j >> 1);
+        m1[j >> 2] |= v1 << (8 * (j & 3));
+        m2[j >> 2] |= v2 << (8 * (j & 3));
+      }
+      uint4* dst = rs_lds + (size_t)e * 4;
+      dst[0] = make_uint4(g[0].w[0], g[0].w[1], g[0].w[2], g[0].w[3]);
+      dst[1] = make_uint4(g[1].w[0], g[1].w[1], g[1].w[2], g[1].w[3]);
+      dst[2] = make_uint4(g[2].w[0], g[2].w[1], g[2].w[2], g[2].w[3]);
+      dst[3] = make_uint4(m1[0], m1[1], m2[0], m2[1]);
+    }
+    __syncthreads();
+    if (wave0 >= Ld) continue;  // a wave wholly past the row end only stages tables (uniform)
+    uint32_t acc[CH][D];
+#pragma unroll
+    for (int o = 0; o < CH; o++)
+#pragma unroll
+      for (int j = 0; j < D; j++) acc[o][j] = 0;
+    uint32_t na[D], nb[D], nc[D];
+    load_in(0, na);
+    load_in(1, nb);
+    load_in(2, nc);
+#pragma unroll 1
+    for (uint32_t t = 0; t < nt; t++) {
+      uint32_t a0[D], a1[D], b0[D], b1[D], c0[D], c1[D], s1[D], s2[D];
+#pragma unroll
+      for (int j = 0; j < D; j++) {
+        a0[j] = na[j] & 0x07070707u;
+        a1[j] = (na[j] >> 3) & 0x07070707u;
+        b0[j] = nb[j] & 0x07070707u;
+        b1[j] = (nb[j] >> 3) & 0x07070707u;
+        c0[j] = nc[j] & 0x07070707u;
+        c1[j] = (nc[j] >> 3) & 0x07070707u;
+        s1[j] = ((na[j] >> 6) & 0x03030303u) | ((nb[j] >> 4) & 0x04040404u);
+        s2[j] = ((nb[j] >> 7) & 0x01010101u) | ((nc[j] >> 5) & 0x06060606u);
+      }
+      load_in(3 * t + 3, na);
+      load_in(3 * t + 4, nb);
+      load_in(3 * t + 5, nc);
+      const uint4* tp = rs_lds + (size_t)t * CH * 4;
+#pragma unroll
+      for (int o = 0; o < CH; o++) {
+        const uint4 A = tp[4 * o], B = tp[4 * o + 1], C = tp[4 * o + 2], M = tp[4 * o + 3];
+#pragma unroll
+        for (int j = 0; j < D; j++) {
+          uint32_t x = xor3(acc[o][j], __builtin_amdgcn_perm(A.y, A.x, a0[j]), __builtin_amdgcn_perm(A.w, A.z, a1[j]));
+          x = xor3(x, __builtin_amdgcn_perm(B.y, B.x, b0[j]), __builtin_amdgcn_perm(B.w, B.z, b1[j]));
+          x = xor3(x, __builtin_amdgcn_perm(C.y, C.x, c0[j]), __builtin_amdgcn_perm(C.w, C.z, c1[j]));
+          acc[o][j] = xor3(x, __builtin_amdgcn_perm(M.y, M.x, s1[j]), __builtin_amdgcn_perm(M.w, M.z, s2[j]));
+        }
+      }
+    }
+#pragma unroll
+    for (int o = 0; o < CH; o++) {
+      if (o0 + o < no) {
+        uint32_t* dst = base + (size_t)ld_uniform(&J->out_idx[o0 + o]) * Pd + wave0 + lane;
+#pragma unroll
+        for (int j = 0; j < D; j++)
+          if (ok[j]) dst[64 * j] = acc[o][j];
+      }
+    }
+  }
+}
+
 template <int CH, int D>
 __global__ void __launch_bounds__(256, HBX_RS3_WPE) k_rs_code_perm3(uint8_t* __restrict__ shards, size_t inst_stride, uint32_t L,
                                                        uint32_t k, const rs_job* __restrict__ jobs,
@@ -407,6 +524,24 @@ __global__ void __launch_bounds__(256, HBX_RS3_WPE) k_rs_code_perm3(uint8_t* __r
     }
   }
 }
+
+// The same coding over the ragged layout (include/hbx.h): instance q's rows are the
+// ceil(len / 4) dwords at buf + off + r * pitch (off, pitch % 4 == 0, so every row is a dword
+// row whatever its length; the pad bytes of the last dword are coded along and are nobody's
+// result).  grid (ceil(max row dwords / (256 * D)), inst, passes): the column grid is the
+// largest instance's, and a block past its own instance's row end leaves before it stages tables.
+template <int CH, int D>
+__global__ void __launch_bounds__(256, HBX_RS3_WPE) k_rs_code_perm3_rg(uint8_t* __restrict__ buf,
+                                                       const rg_desc* __restrict__ desc,
+                                                       uint32_t k, const rs_job* __restrict__ jobs,
+                                                       const gf_ptab* __restrict__ tables, uint32_t job_stride) {
+  const uint32_t inst = blockIdx.y;
+  const uint32_t Ld = (ld_uniform(&desc[inst].len) + 3) >> 2;
+  if (blockIdx.x * 256 * D >= Ld) return;
+  rs_perm3_block<CH, D>(reinterpret_cast<uint32_t*>(buf + ld_uniform(&desc[inst].off)), Ld,
+                        ld_uniform(&desc[inst].pitch) >> 2, k, jobs + (size_t)inst * job_stride,
+                        tables + (size_t)inst * job_stride * RS_MAX_N * k);
+}
 #endif
 #if defined(HBX_TU) && HBX_TU == 6
 // the tiles rs_code() (hbx_api.hip) launches, instantiated in this translation unit
@@ -431,6 +566,15 @@ HBX_RS_INST3(21, 2)
 HBX_RS_INST3(28, 2)
 HBX_RS_INST3(42, 2)
 #undef HBX_RS_INST3
+#define HBX_RS_INST3RG(ch, d)                                                                                \
+  template __global__ void k_rs_code_perm3_rg<ch, d>(uint8_t* __restrict__, const rg_desc* __restrict__, uint32_t, \
+                                                      const rs_job* __restrict__, const gf_ptab* __restrict__, uint32_t);
+HBX_RS_INST3RG(12, 2)
+HBX_RS_INST3RG(14, 2)
+HBX_RS_INST3RG(21, 2)
+HBX_RS_INST3RG(28, 2)
+HBX_RS_INST3RG(42, 2)
+#undef HBX_RS_INST3RG
 #endif
 
 // reconstruct_shards set-up, one block per instance (reed-solomon-erasure 3.1.0):
@@ -733,6 +877,7 @@ __device__ __forceinline__ void merkle_node(int variant, const uint32_t* l8, con
 // of `row` bytes (hbx_merkle_validate_d): leaf i hashes the whole value, its first byte in the
 // prefix position and the other L = row - 1 bytes as the data.
 constexpr uint32_t MERKLE_NO_SLOT = 0xFFFFu;
+constexpr uint32_t VAL_NONE = 0xFFFFFFFFu;  // unused lane of a ragged value block (k_merkle_values_*_rg)
 
 // SHA-256 Merkle leaves (HBX_MERKLE_SHA256), two waves per 64 leaves of one instance:
 //  * wave 1 (producer) loads each leaf's next 64-byte block, expands the message schedule and
@@ -748,6 +893,110 @@ __device__ __forceinline__ uint32_t sha_sig(uint32_t x, int r1, int r2, int r3) 
 }
 
 #if HBX_IN_TU(6)
+// k_merkle_leaves_sha256's schedule for one block of 64 leaves (both waves), for the ragged kernels
+// below: lane's leaf = SHA-256(0x00 || prefix byte || data[L]) with `prefix` = that byte << 8; L is
+// block-uniform, a lane that is not `live` hashes along (its data pointer must be readable) and
+// stores nothing.  Digest words to o[0..8).
+__device__ __forceinline__ void merkle_leaves_sha256_block(const uint8_t* data, uint32_t prefix, uint32_t L, bool live,
+                                                           uint32_t* o) {
+  __shared__ uint4 kw[2][16][64];  // [slot][rounds / 4][lane]
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t total = 2 + (uint64_t)L;
+  const uint64_t nblocks = (total + 9 + 63) / 64;
+  // producer state: raw dwords of the next block (fast blocks: whole 64 bytes of shard data)
+  uint32_t raw[17];
+  auto fast = [&](uint64_t b) { return b * 64 >= 2 && b * 64 + 64 <= total; };
+  auto fetch = [&](uint64_t b) {
+    if (b < nblocks && fast(b)) {
+      const uint8_t* q = data + (b * 64 - 2);
+      const uint32_t* pa = reinterpret_cast<const uint32_t*>((uintptr_t)q & ~(uintptr_t)3);
+#pragma unroll
+      for (int k = 0; k < 16; k++) raw[k] = pa[k];
+      // a misaligned block needs a 17th dword (it holds block bytes, so it is inside the buffer)
+      raw[16] = ((uintptr_t)q & 3) ? pa[16] : 0u;
+    }
+  };
+  auto produce = [&](uint64_t b, int slot) {
+    uint32_t w[16];
+    if (fast(b)) {
+      const uint32_t sh = (uint32_t)(((uintptr_t)data + b * 64 - 2) & 3);
+#pragma unroll
+      for (int k = 0; k < 16; k++) w[k] = bswap32(__builtin_amdgcn_alignbyte(raw[k + 1], raw[k], sh));
+    } else {
+      const uint64_t b0 = b * 64;
+#pragma unroll 1
+      for (int k = 0; k < 16; k++) {
+        uint32_t word = 0;
+        for (int q = 0; q < 4; q++) {
+          const uint64_t pos = b0 + 4 * k + q;
+          uint8_t byte;
+          if (pos < total) byte = msg_byte(prefix, 2, data, L, pos);
+          else if (pos == total) byte = 0x80;
+          else if (pos >= nblocks * 64 - 8) byte = (uint8_t)((total * 8) >> (8 * (nblocks * 64 - 1 - pos)));
+          else byte = 0;
+          word = (word << 8) | byte;
+        }
+        w[k] = word;
+      }
+    }
+    fetch(b + 1);  // next block's raw words load while this schedule is expanded
+#pragma unroll
+    for (int t4 = 0; t4 < 16; t4++) {
+      uint32_t o[4];
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int t = 4 * t4 + q;
+        uint32_t wt;
+        if (t < 16) {
+          wt = w[t];
+        } else {
+          const uint32_t w15 = w[(t + 1) & 15], w2 = w[(t + 14) & 15];
+          const uint32_t s0 = xor3(rotr32(w15, 7), rotr32(w15, 18), w15 >> 3);
+          const uint32_t s1 = xor3(rotr32(w2, 17), rotr32(w2, 19), w2 >> 10);
+          wt = w[t & 15] + s0 + w[(t + 9) & 15] + s1;
+          w[t & 15] = wt;
+        }
+        o[q] = wt + SHA256_K[t];
+      }
+      kw[slot][t4][lane] = make_uint4(o[0], o[1], o[2], o[3]);
+    }
+  };
+  uint32_t H[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
+                   0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
+  if (wave == 1) {
+    fetch(0);
+    produce(0, 0);
+  }
+  __syncthreads();
+  for (uint64_t b = 0; b < nblocks; b++) {
+    const int slot = (int)(b & 1);
+    if (wave == 0) {
+      uint32_t a = H[0], bb = H[1], c = H[2], d = H[3], e = H[4], f = H[5], g = H[6], h = H[7];
+#pragma unroll
+      for (int t4 = 0; t4 < 16; t4++) {
+        const uint4 k4 = kw[slot][t4][lane];
+        const uint32_t kv[4] = {k4.x, k4.y, k4.z, k4.w};
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          // Ch and Maj as one v_bitop3 each (truth tables 0xCA: e ? f : g, 0xE8: majority); the
+          // compiler's own Maj took three ops (14 VALU per round instead of 16)
+          const uint32_t t1 = h + kv[q] + sha_sig(e, 6, 11, 25) + __builtin_amdgcn_bitop3_b32(e, f, g, 0xCA);
+          const uint32_t t2 = sha_sig(a, 2, 13, 22) + __builtin_amdgcn_bitop3_b32(a, bb, c, 0xE8);
+          h = g; g = f; f = e; e = d + t1; d = c; c = bb; bb = a; a = t1 + t2;
+        }
+      }
+      H[0] += a; H[1] += bb; H[2] += c; H[3] += d; H[4] += e; H[5] += f; H[6] += g; H[7] += h;
+    } else if (b + 1 < nblocks) {
+      produce(b + 1, slot ^ 1);
+    }
+    __syncthreads();
+  }
+  if (wave == 0 && live) {
+#pragma unroll
+    for (int q = 0; q < 8; q++) o[q] = H[q];
+  }
+}
+
 __global__ void __launch_bounds__(128) k_merkle_leaves_sha256(const uint8_t* __restrict__ shards, size_t inst_stride,
                                                               uint32_t n, uint32_t L, uint32_t* __restrict__ leaf_hash,
                                                               const uint16_t* __restrict__ slots, uint32_t nslots,
@@ -859,6 +1108,43 @@ __global__ void __launch_bounds__(128) k_merkle_leaves_sha256(const uint8_t* __r
 #pragma unroll
     for (int q = 0; q < 8; q++) o[q] = H[q];
   }
+}
+
+// Ragged forms (include/hbx.h).  Leaves of the instances of one buffer: blockIdx.y = instance, so
+// L = len[inst] stays block-uniform and the producer / consumer lockstep is the uniform kernel's;
+// row i is at off + i * pitch.  slots as above.  grid (ceil(n / 64), inst), 128 threads.
+__global__ void __launch_bounds__(128) k_merkle_leaves_sha256_rg(const uint8_t* __restrict__ buf,
+                                                                 const rg_desc* __restrict__ desc, uint32_t n,
+                                                                 uint32_t* __restrict__ leaf_hash,
+                                                                 const uint16_t* __restrict__ slots, uint32_t nslots) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t inst = blockIdx.y;
+  uint32_t i = blockIdx.x * 64 + lane;
+  if (slots) i = i < nslots ? slots[(size_t)inst * nslots + i] : MERKLE_NO_SLOT;
+  const bool live = i < n;
+  if (!__syncthreads_or(live ? 1 : 0)) return;
+  const uint8_t* data = buf + ld_uniform(&desc[inst].off) + (size_t)(live ? i : 0) * ld_uniform(&desc[inst].pitch);
+  merkle_leaves_sha256_block(data, (i & 0xFF) << 8, ld_uniform(&desc[inst].len), live,
+                             leaf_hash + ((size_t)inst * n + i) * 8);
+}
+
+// Leaf digests of proof values of any lengths (hbx_merkle_validate_ragged_d): the host sorts the
+// long values into blocks of one length; block b hashes the values idx[b][0..64) (VAL_NONE =
+// unused lane) of vlen[b] bytes each, value j at values + val_off[j], its first byte in the prefix
+// position.  Digest j to digest[j][8].  grid (blocks), 128 threads.
+__global__ void __launch_bounds__(128) k_merkle_values_sha256_rg(const uint8_t* __restrict__ values,
+                                                                 const uint64_t* __restrict__ val_off,
+                                                                 const uint32_t* __restrict__ vlen,
+                                                                 const uint32_t* __restrict__ idx,
+                                                                 uint32_t* __restrict__ digest) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t j = idx[(size_t)blockIdx.x * 64 + lane];
+  const bool live = j != VAL_NONE;
+  // a dead lane hashes along on the block's first value (the host fills blocks from lane 0)
+  const uint32_t jr = live ? j : idx[(size_t)blockIdx.x * 64];
+  const uint8_t* data = values + val_off[jr] + 1;
+  merkle_leaves_sha256_block(data, (uint32_t)data[-1] << 8, ld_uniform(&vlen[blockIdx.x]) - 1, live,
+                             digest + (size_t)jr * 8);
 }
 #endif
 
@@ -993,6 +1279,68 @@ __device__ __forceinline__ void keccak_f1600_il(uint32_t* a, uint32_t h) {
   }
 }
 
+// k_merkle_leaves_sha3's hashing of one lane pair's leaf, for the ragged kernels below:
+// SHA3-256(prefix byte || data[L]) (h = this lane's half); digest words to o[0..8) by the even
+// lane.  Whole pairs call this or neither lane does.
+__device__ __forceinline__ void merkle_leaf_sha3_pair(const uint8_t* data, uint32_t prefix, uint32_t L, uint32_t h,
+                                                      uint32_t* o) {
+  const uint64_t total = 1 + (uint64_t)L;
+  const uint64_t nblocks = total / 136 + 1;
+  uint32_t a[25];
+#pragma unroll
+  for (int q = 0; q < 25; q++) a[q] = 0;
+  for (uint64_t blk = 0; blk < nblocks; blk++) {
+    const uint64_t b0 = blk * 136;
+    if (b0 >= 1 && b0 + 136 <= total) {
+      const uint8_t* q = data + (b0 - 1);
+      const uintptr_t ad = (uintptr_t)q;
+      const uint32_t* pa = reinterpret_cast<const uint32_t*>(ad & ~(uintptr_t)3);
+      const uint32_t sh = (uint32_t)(ad & 3);
+      uint32_t d[35];
+#pragma unroll
+      for (int k = 0; k < 34; k++) d[k] = pa[k];
+      d[34] = sh ? pa[34] : 0u;
+#pragma unroll
+      for (int w = 0; w < 17; w++) {
+        const uint32_t lo = __builtin_amdgcn_alignbyte(d[2 * w + 1], d[2 * w], sh);
+        const uint32_t hi = __builtin_amdgcn_alignbyte(d[2 * w + 2], d[2 * w + 1], sh);
+        a[w] ^= ileave_half(lo, hi, h);
+      }
+    } else {
+#pragma unroll 1
+      for (int w = 0; w < 17; w++) {
+        uint32_t lo = 0, hi = 0;
+        for (int k = 0; k < 8; k++) {
+          const uint64_t pos = b0 + 8 * w + k;
+          uint8_t byte = pos < total ? msg_byte(prefix, 1, data, L, pos) : 0;
+          if (pos == total) byte ^= 0x06;
+          if (blk == nblocks - 1 && 8 * w + k == 135) byte ^= 0x80;
+          if (k < 4) lo |= (uint32_t)byte << (8 * k);
+          else hi |= (uint32_t)byte << (8 * (k - 4));
+        }
+        a[w] ^= ileave_half(lo, hi, h);
+      }
+    }
+    keccak_f1600_il(a, h);
+  }
+  // digest bytes 0..31 = state words 0..3, little-endian; out as 8 big-endian words
+  uint32_t out[8];
+  dpp_guard_pairs();
+#pragma unroll
+  for (int w = 0; w < 4; w++) {
+    const uint32_t mine = a[w], other = k_xchg(a[w]);
+    const uint32_t e = h ? other : mine, o = h ? mine : other;
+    const uint32_t lo = spread16(e) | (spread16(o) << 1);
+    const uint32_t hi = spread16(e >> 16) | (spread16(o >> 16) << 1);
+    out[2 * w] = bswap32(lo);
+    out[2 * w + 1] = bswap32(hi);
+  }
+  if (h == 0) {
+#pragma unroll
+    for (int q = 0; q < 8; q++) o[q] = out[q];
+  }
+}
+
 __global__ void __launch_bounds__(64) k_merkle_leaves_sha3(const uint8_t* __restrict__ shards, size_t inst_stride,
                                                            uint32_t n, uint32_t L, uint32_t* __restrict__ leaf_hash,
                                                            const uint16_t* __restrict__ slots, uint32_t nslots,
@@ -1059,6 +1407,32 @@ __global__ void __launch_bounds__(64) k_merkle_leaves_sha3(const uint8_t* __rest
 #pragma unroll
     for (int q = 0; q < 8; q++) o[q] = out[q];
   }
+}
+
+// Ragged forms, as k_merkle_leaves_sha256_rg / k_merkle_values_sha256_rg (32 leaves or values per
+// 64-thread block).
+__global__ void __launch_bounds__(64) k_merkle_leaves_sha3_rg(const uint8_t* __restrict__ buf,
+                                                              const rg_desc* __restrict__ desc, uint32_t n,
+                                                              uint32_t* __restrict__ leaf_hash,
+                                                              const uint16_t* __restrict__ slots, uint32_t nslots) {
+  const uint32_t inst = blockIdx.y, lane = threadIdx.x, h = lane & 1u;
+  uint32_t i = blockIdx.x * 32 + (lane >> 1);
+  if (slots) i = i < nslots ? slots[(size_t)inst * nslots + i] : MERKLE_NO_SLOT;
+  if (i >= n) return;  // whole pairs
+  const uint8_t* data = buf + ld_uniform(&desc[inst].off) + (size_t)i * ld_uniform(&desc[inst].pitch);
+  merkle_leaf_sha3_pair(data, i & 0xFF, ld_uniform(&desc[inst].len), h, leaf_hash + ((size_t)inst * n + i) * 8);
+}
+
+__global__ void __launch_bounds__(64) k_merkle_values_sha3_rg(const uint8_t* __restrict__ values,
+                                                              const uint64_t* __restrict__ val_off,
+                                                              const uint32_t* __restrict__ vlen,
+                                                              const uint32_t* __restrict__ idx,
+                                                              uint32_t* __restrict__ digest) {
+  const uint32_t lane = threadIdx.x, h = lane & 1u;
+  const uint32_t j = idx[(size_t)blockIdx.x * 32 + (lane >> 1)];
+  if (j == VAL_NONE) return;  // whole pairs
+  const uint8_t* data = values + val_off[j] + 1;
+  merkle_leaf_sha3_pair(data, (uint32_t)data[-1], ld_uniform(&vlen[blockIdx.x]) - 1, h, digest + (size_t)j * 8);
 }
 #endif
 
@@ -1190,6 +1564,55 @@ __global__ void __launch_bounds__(64) k_merkle_proofs(const uint8_t* __restrict_
 // nodes = node_hash + j * 17 * 32 (root first, leaf hash last), sibs = sib_hash + j * 16 * 32,
 // sides bit k set = sibling at level k is on the LEFT (merkle.rs Positioned::Left).
 #if HBX_IN_TU(6)
+// k_merkle_validate's check of proof j with the value given by pointer and length (the ragged kernel)
+__device__ __forceinline__ void merkle_validate_one(const uint8_t* val, uint32_t vlen, uint32_t j, const uint8_t* node_hash,
+                                                    const uint8_t* sib_hash, const uint32_t* sides,
+                                                    const uint32_t* depth, const uint8_t* root_hash,
+                                                    const uint32_t* sender, uint32_t count, uint8_t* valid,
+                                                    int variant, const uint32_t* vdigest) {
+  const uint32_t d = depth[j];
+  const uint8_t* nodes = node_hash + (size_t)j * 17 * 32;
+  const uint8_t* sibs = sib_hash + (size_t)j * 16 * 32;
+  bool ok = d <= 16 && vlen >= 1;
+  for (int q = 0; q < 32 && ok; q++) ok = root_hash[(size_t)j * 32 + q] == nodes[q];
+  auto be8 = [](const uint8_t* p, uint32_t* w) {
+    for (int q = 0; q < 8; q++)
+      w[q] = ((uint32_t)p[4 * q] << 24) | ((uint32_t)p[4 * q + 1] << 16) | ((uint32_t)p[4 * q + 2] << 8) | p[4 * q + 3];
+  };
+  uint32_t h[8], want[8], a[8], b[8];
+  if (ok) {
+    if (vdigest) {  // the values' leaf digests, hashed beforehand by the leaf kernels
+#pragma unroll
+      for (int q = 0; q < 8; q++) h[q] = vdigest[(size_t)j * 8 + q];
+    } else {
+      merkle_leaf_value(variant, val, vlen, h);
+    }
+    be8(nodes + (size_t)d * 32, want);
+    for (int q = 0; q < 8; q++) ok = ok && h[q] == want[q];
+  }
+  for (uint32_t lv = 0; lv < d && ok; lv++) {
+    be8(sibs + (size_t)lv * 32, a);
+    be8(nodes + (size_t)(lv + 1) * 32, b);
+    if ((sides[j] >> lv) & 1) merkle_node(variant, a, b, h);
+    else merkle_node(variant, b, a, h);
+    be8(nodes + (size_t)lv * 32, want);
+    for (int q = 0; q < 8; q++) ok = ok && h[q] == want[q];
+  }
+  // Proof::index(count) from the Left/Right path
+  uint32_t idx = 0, c = count;
+  for (uint32_t lv = 0; lv < d; lv++) {
+    const uint32_t left = c > 1 ? 1u << (31 - __clz(c - 1)) : 1u;
+    if ((sides[j] >> lv) & 1) {
+      idx += left;
+      c -= left;
+    } else {
+      c = left;
+    }
+  }
+  ok = ok && val[0] == sender[j] && idx == val[0];
+  valid[j] = ok ? 1 : 0;
+}
+
 __global__ void __launch_bounds__(64) k_merkle_validate(const uint8_t* __restrict__ values, uint32_t vlen,
                                                         const uint8_t* __restrict__ node_hash,
                                                         const uint8_t* __restrict__ sib_hash,
@@ -1244,6 +1667,27 @@ __global__ void __launch_bounds__(64) k_merkle_validate(const uint8_t* __restric
   ok = ok && val[0] == sender[j] && idx == val[0];
   valid[j] = ok ? 1 : 0;
 }
+
+// The ragged form (hbx_merkle_validate_ragged_d): value j is values[val_off[j], val_off[j + 1]),
+// of any length; a value longer than 256 bytes has its digest in vdigest[j] (k_merkle_values_*_rg),
+// a shorter one is hashed in the lane, an empty one is invalid (never read).
+__global__ void __launch_bounds__(64) k_merkle_validate_rg(const uint8_t* __restrict__ values,
+                                                           const uint64_t* __restrict__ val_off,
+                                                           const uint8_t* __restrict__ node_hash,
+                                                           const uint8_t* __restrict__ sib_hash,
+                                                           const uint32_t* __restrict__ sides,
+                                                           const uint32_t* __restrict__ depth,
+                                                           const uint8_t* __restrict__ root_hash,
+                                                           const uint32_t* __restrict__ sender, uint32_t count,
+                                                           uint32_t nproofs, uint8_t* __restrict__ valid, int variant,
+                                                           const uint32_t* __restrict__ vdigest) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= nproofs) return;
+  const uint64_t o0 = val_off[j];
+  const uint32_t vlen = (uint32_t)(val_off[j + 1] - o0);
+  merkle_validate_one(values + o0, vlen, j, node_hash, sib_hash, sides, depth, root_hash, sender, count, valid, variant,
+                      vlen > 256 ? vdigest : nullptr);
+}
 #endif
 
 // glue_shards (broadcast.rs:697-707): the payload is bytes [4, 4 + len) of the first k shards
@@ -1289,6 +1733,73 @@ __global__ void __launch_bounds__(256) k_glue(const uint8_t* __restrict__ shards
   } else {
     const uint64_t end = q0 + 16 < len ? 16 : len - q0;
     for (uint64_t q = 0; q < end; q++) dst[q] = src[q];
+  }
+}
+#endif
+
+// glue_shards over the ragged layout: with pitch != len the first k shards are not contiguous, so
+// payload byte p is byte (p + 4) % L of row (p + 4) / L -- a row-wise gather.  Instance q's
+// payload goes to out + out_off[q] (the host checked the room for k L - 4 bytes).  grid
+// (ceil(max k len / 4096), inst): thread = 16 output bytes; four dword loads and stores when they lie
+// inside one row with source and destination dword-aligned, else dword by dword where a dword
+// does, and byte copies for the rest.
+#if HBX_IN_TU(6)
+__global__ void __launch_bounds__(256) k_glue_rg(const uint8_t* __restrict__ buf, const rg_desc* __restrict__ desc,
+                                                 uint32_t k, uint8_t* __restrict__ out,
+                                                 const uint64_t* __restrict__ out_off, uint64_t* __restrict__ out_len,
+                                                 int32_t* __restrict__ status) {
+  const uint32_t inst = blockIdx.y;
+  const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
+  if (status[inst] != 0) {
+    if (lead) out_len[inst] = 0;
+    return;
+  }
+  const uint32_t L = ld_uniform(&desc[inst].len), P = ld_uniform(&desc[inst].pitch);
+  const uint8_t* base = buf + ld_uniform(&desc[inst].off);
+  const uint64_t total = (uint64_t)k * L;
+  if (total < 4) {
+    if (lead) {
+      status[inst] = -11;
+      out_len[inst] = 0;
+    }
+    return;
+  }
+  // the header is stream bytes 0..3: row b / L, column b % L (L may be below 4)
+  uint64_t want = 0;
+  for (uint32_t b = 0; b < 4; b++) want = (want << 8) | base[(size_t)(b / L) * P + b % L];
+  const uint64_t len = want < total - 4 ? want : total - 4;
+  if (lead) out_len[inst] = len;
+  const uint64_t q0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
+  if (q0 >= len) return;
+  uint8_t* dst = out + out_off[inst] + q0;
+  // one division per thread, then (row, col) step along the stream
+  const uint64_t sp = q0 + 4;
+  uint32_t row = (uint32_t)(sp / L), col = (uint32_t)(sp - (uint64_t)row * L);
+  const uint8_t* src = base + (size_t)row * P + col;
+  if (q0 + 16 <= len && col + 16 <= L && (((uintptr_t)src | (uintptr_t)dst) & 3) == 0) {
+    const uint32_t* s4 = reinterpret_cast<const uint32_t*>(src);
+    uint32_t* d4 = reinterpret_cast<uint32_t*>(dst);
+    const uint32_t v0 = s4[0], v1 = s4[1], v2 = s4[2], v3 = s4[3];
+    d4[0] = v0;
+    d4[1] = v1;
+    d4[2] = v2;
+    d4[3] = v3;
+    return;
+  }
+  const uint32_t end = q0 + 16 < len ? 16u : (uint32_t)(len - q0);
+  for (uint32_t b = 0; b < end;) {
+    src = base + (size_t)row * P + col;
+    uint32_t step;
+    if (b + 4 <= end && col + 4 <= L && (((uintptr_t)src | (uintptr_t)(dst + b)) & 3) == 0) {
+      *reinterpret_cast<uint32_t*>(dst + b) = *reinterpret_cast<const uint32_t*>(src);
+      step = 4;
+    } else {
+      dst[b] = *src;
+      step = 1;
+    }
+    b += step;
+    col += step;
+    if (col >= L) col -= L, row++;
   }
 }
 #endif

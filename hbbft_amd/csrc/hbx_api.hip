@@ -4,6 +4,7 @@
 // HBX_E_DEVICE.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -111,6 +112,14 @@ struct hbx_ctx {
   dbuf gf_log, gf_exp;
   uint32_t rs_k = 0, rs_m = 0;
   dbuf rs_enc, rs_enc_job, rs_enc_coef, rs_enc_ptab, rs_ptab_d, rs_ptab_p, rs_jobs_d, rs_jobs_p, rs_coef_d, rs_coef_p, leaf_hash, leaf_slots, val_digest, roots;
+  // ragged broadcast calls: the call's host descriptors are copied into pinned staging (rg_pin)
+  // and uploaded to rg_dev in one async copy; rg_ev marks the end of that copy, the only thing a
+  // later call waits for on the host (before it rewrites the staging)
+  dbuf rg_dev;
+  void* rg_pin = nullptr;
+  size_t rg_pin_cap = 0;
+  hipEvent_t rg_ev = nullptr;
+  bool rg_ev_recorded = false;
   // common coin state: nonces' hash_g2 points and lines, signature shares, combined signatures
   uint32_t coin_I = 0, coin_n = 0;
   dbuf coin_blob, coin_off, coin_H, coin_Hp, coin_lines, coin_scratch, coin_sk, coin_sig96, coin_sig, coin_sig_st, coin_present,
@@ -626,8 +635,10 @@ int hbx_ctx_destroy(hbx_ctx* c) {
                   &c->vs_sig, &c->vs_sig_st, &c->vs_status, &c->fe1slot, &c->fb_lanes, &c->fb_coin, &c->hs[0], &c->hs[1], &c->hs[2], &c->hs[3], &c->hs[4], &c->hs[5], &c->coin_use, &c->bv_commit48, &c->bv_C, &c->bv_cst, &c->bv_rows,
                   &c->bv_rows48, &c->bv_pst, &c->bv_ackp, &c->bv_acky, &c->bv_vals, &c->bv_out,
                   &c->kg_sk, &c->kg_out, &c->kg_st, &c->b_seed, &c->b_AJ, &c->b_T, &c->b_C, &c->b_Asum, &c->b_A, &c->b_B,
-                  &c->b_cls0, &c->b_cand, &c->b_pass, &c->b_zero, &c->b_cls, &c->b_ctok, &c->b_stats};
+                  &c->b_cls0, &c->b_cand, &c->b_pass, &c->b_zero, &c->b_cls, &c->b_ctok, &c->b_stats, &c->rg_dev};
   for (dbuf* b : bufs) b->release();
+  if (c->rg_pin) (void)hipHostFree(c->rg_pin);
+  if (c->rg_ev) (void)hipEventDestroy(c->rg_ev);
   (void)hipEventDestroy(c->ev_last);
   if (c->coin_ready_ev) (void)hipEventDestroy(c->coin_ready_ev);
   (void)hipStreamDestroy(c->stream);
@@ -1269,6 +1280,348 @@ int hbx_broadcast_decode_leaves_d(hbx_ctx* c, uint8_t* d_shards, const uint8_t* 
   if (!d_leaf_hash) return fail(c, HBX_E_INVALID_ARG, "hbx_broadcast_decode_leaves_d: d_leaf_hash is NULL");
   return broadcast_decode(c, d_shards, d_present, d_leaf_hash, d_root_expect, inst, k, m, L, d_out, out_stride,
                           d_out_len, d_status, stream);
+}
+
+// ---- Broadcast, ragged forms (include/hbx.h): per-instance shard lengths in one call -----------
+// The host descriptors of a call (rg_desc per instance, and the call's other host arrays) are
+// laid out in the context's pinned staging buffer and uploaded with one asynchronous copy on the
+// call's stream, so the caller's arrays are consumed at return and nothing waits for the device
+// -- except a later ragged call, which waits for the previous upload (not the previous kernels)
+// before it rewrites the staging, and rs_setup's one-off synchronisation per (k, m).
+static uint8_t* rg_begin(hbx_ctx* c, size_t bytes) {
+  if (c->rg_ev_recorded && hipEventSynchronize(c->rg_ev) != hipSuccess) return nullptr;
+  c->rg_ev_recorded = false;
+  if (bytes > c->rg_pin_cap) {
+    if (c->rg_pin) (void)hipHostFree(c->rg_pin);
+    c->rg_pin = nullptr;
+    c->rg_pin_cap = 0;
+    const size_t cap = bytes + bytes / 2 + 4096;
+    if (hipHostMalloc(&c->rg_pin, cap, hipHostMallocDefault) != hipSuccess) return nullptr;
+    c->rg_pin_cap = cap;
+  }
+  if (!c->rg_ev && hipEventCreateWithFlags(&c->rg_ev, hipEventDisableTiming) != hipSuccess) return nullptr;
+  if (!c->rg_dev.ensure(bytes)) return nullptr;
+  return static_cast<uint8_t*>(c->rg_pin);
+}
+
+static int rg_upload(hbx_ctx* c, size_t bytes, hipStream_t s) {
+  HIPCHK(c, hipMemcpyAsync(c->rg_dev.p, c->rg_pin, bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipEventRecord(c->rg_ev, s));
+  c->rg_ev_recorded = true;
+  return HBX_OK;
+}
+
+// The descriptor rules of include/hbx.h; max_len = the longest shard.
+static int rg_check(hbx_ctx* c, const char* fn, uint64_t buf_bytes, const uint64_t* off, const uint32_t* len,
+                    const uint32_t* pitch, uint32_t inst, uint32_t n, uint32_t* max_len) {
+  if (!off || !len || !pitch || inst == 0 || n == 0) return fail(c, HBX_E_INVALID_ARG, "%s: bad args", fn);
+  uint32_t mx = 0;
+  for (uint32_t q = 0; q < inst; q++) {
+    if (off[q] % 4 || pitch[q] % 4)
+      return fail(c, HBX_E_INVALID_ARG, "%s: instance %u: off %llu and pitch %u must be multiples of 4", fn, q,
+                  (unsigned long long)off[q], pitch[q]);
+    if (len[q] == 0 || pitch[q] < len[q])
+      return fail(c, HBX_E_INVALID_ARG, "%s: instance %u: need pitch %u >= len %u >= 1", fn, q, pitch[q], len[q]);
+    if (off[q] > buf_bytes || (uint64_t)n * pitch[q] > buf_bytes - off[q])
+      return fail(c, HBX_E_INVALID_ARG, "%s: instance %u: rows [%llu, +%u x %u) end past the buffer (%llu bytes)", fn, q,
+                  (unsigned long long)off[q], n, pitch[q], (unsigned long long)buf_bytes);
+    if (len[q] > mx) mx = len[q];
+  }
+  std::vector<uint32_t> order(inst);
+  for (uint32_t q = 0; q < inst; q++) order[q] = q;
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return off[a] < off[b]; });
+  for (uint32_t r = 1; r < inst; r++) {
+    const uint32_t a = order[r - 1], b = order[r];
+    if (off[b] < off[a] + (uint64_t)n * pitch[a])
+      return fail(c, HBX_E_INVALID_ARG, "%s: instances %u and %u overlap", fn, a, b);
+  }
+  *max_len = mx;
+  return HBX_OK;
+}
+
+static void rg_fill(rg_desc* d, const uint64_t* off, const uint32_t* len, const uint32_t* pitch, uint32_t inst) {
+  for (uint32_t q = 0; q < inst; q++) d[q] = rg_desc{off[q], len[q], pitch[q]};
+}
+
+// One ragged coding pass: the triple byte-permute kernel, tiled by output count as rs_code tiles it
+// (rows are dword rows by construction, so the LDS log/exp byte kernel has no part here; the
+// 12-row tile's tables fit the LDS for every k <= 128).
+static void rs_code_rg(hbx_ctx* c, uint8_t* d_buf, const rg_desc* d_desc, uint32_t max_len, uint32_t k, uint32_t inst,
+                       const rs_job* jobs, const gf_ptab* ptab, uint32_t job_stride, uint32_t no, hipStream_t s) {
+  timed t_(c, HBX_K_RS_CODE, s);
+  if (no == 0) no = 1;
+  const uint32_t Ld = (max_len + 3) / 4;
+  static const int ch3[] = {21, 14, 12, 28, 42};
+  int ch = 12, best_rows = 1 << 30;
+  for (int t : ch3) {
+    if (rs_perm3_lds_bytes(k, t) > 65536) continue;
+    const int rows = (int)((no + t - 1) / t) * t;
+    if (rows < best_rows) ch = t, best_rows = rows;
+  }
+  switch (ch) {
+#define HBX_RS_TILE3RG(c3)                                                                                            \
+  hipLaunchKernelGGL((k_rs_code_perm3_rg<c3, 2>), dim3((Ld + 511) / 512, inst, (no + c3 - 1) / c3), dim3(256),         \
+                     rs_perm3_lds_bytes(k, c3), s, d_buf, d_desc, k, jobs, ptab, job_stride);                          \
+  break;
+    case 42: HBX_RS_TILE3RG(42)
+    case 28: HBX_RS_TILE3RG(28)
+    case 14: HBX_RS_TILE3RG(14)
+    case 12: HBX_RS_TILE3RG(12)
+    default: HBX_RS_TILE3RG(21)
+#undef HBX_RS_TILE3RG
+  }
+}
+
+static int rs_reconstruct_rg(hbx_ctx* c, uint8_t* d_buf, const rg_desc* d_desc, uint32_t max_len,
+                             const uint8_t* d_present, uint32_t inst, uint32_t k, uint32_t m, int32_t* d_status,
+                             hipStream_t s) {
+  const size_t tab = (size_t)inst * RS_MAX_N * k;
+  if (!c->rs_jobs_d.ensure((size_t)inst * sizeof(rs_job)) || !c->rs_jobs_p.ensure((size_t)inst * sizeof(rs_job)) ||
+      !c->rs_coef_d.ensure(tab * 2) || !c->rs_coef_p.ensure(tab * 2) || !c->rs_ptab_d.ensure(tab * sizeof(gf_ptab)) ||
+      !c->rs_ptab_p.ensure(tab * sizeof(gf_ptab)))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "rs_reconstruct: out of device memory");
+  hipLaunchKernelGGL(k_rs_setup_reconstruct, dim3(inst), dim3(256), 0, s, d_present, k, m, c->rs_enc.as<uint8_t>(),
+                     c->gf_log.as<uint16_t>(), c->gf_exp.as<uint8_t>(), c->rs_jobs_d.as<rs_job>(),
+                     c->rs_coef_d.as<uint16_t>(), c->rs_jobs_p.as<rs_job>(), c->rs_coef_p.as<uint16_t>(), d_status);
+  const dim3 tg((RS_MAX_N * k + 255) / 256, inst);
+  hipLaunchKernelGGL(k_rs_perm_tables, tg, dim3(256), 0, s, c->rs_jobs_d.as<rs_job>(), c->rs_coef_d.as<uint16_t>(), k,
+                     c->gf_log.as<uint16_t>(), c->gf_exp.as<uint8_t>(), c->rs_ptab_d.as<gf_ptab>());
+  hipLaunchKernelGGL(k_rs_perm_tables, tg, dim3(256), 0, s, c->rs_jobs_p.as<rs_job>(), c->rs_coef_p.as<uint16_t>(), k,
+                     c->gf_log.as<uint16_t>(), c->gf_exp.as<uint8_t>(), c->rs_ptab_p.as<gf_ptab>());
+  HIPCHK(c, hipGetLastError());
+  rs_code_rg(c, d_buf, d_desc, max_len, k, inst, c->rs_jobs_d.as<rs_job>(), c->rs_ptab_d.as<gf_ptab>(), 1u, (m + 1) / 2, s);
+  rs_code_rg(c, d_buf, d_desc, max_len, k, inst, c->rs_jobs_p.as<rs_job>(), c->rs_ptab_p.as<gf_ptab>(), 1u, (m + 1) / 2, s);
+  HIPCHK(c, hipGetLastError());
+  return HBX_OK;
+}
+
+// Leaf digests (all leaves, or the `nslots` listed per instance) into c->leaf_hash, then the trees.
+static int merkle_tree_rg(hbx_ctx* c, const uint8_t* d_buf, const rg_desc* d_desc, uint32_t inst, uint32_t n,
+                          const uint16_t* slots, uint32_t nslots, bool leaves, uint8_t* d_roots, uint8_t* d_nodes,
+                          hipStream_t s) {
+  if (leaves) {
+    timed t_(c, HBX_K_MERKLE_LEAVES, s);
+    const uint32_t cnt = slots ? nslots : n;
+    if (c->merkle == HBX_MERKLE_SHA256)
+      hipLaunchKernelGGL(k_merkle_leaves_sha256_rg, dim3((cnt + 63) / 64, inst), dim3(128), 0, s, d_buf, d_desc, n,
+                         c->leaf_hash.as<uint32_t>(), slots, nslots);
+    else
+      hipLaunchKernelGGL(k_merkle_leaves_sha3_rg, dim3((cnt + 31) / 32, inst), dim3(64), 0, s, d_buf, d_desc, n,
+                         c->leaf_hash.as<uint32_t>(), slots, nslots);
+  }
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_merkle_tree, dim3(inst), dim3(128), 0, s, c->leaf_hash.as<uint32_t>(), n, d_roots, d_nodes,
+                     c->merkle);
+  HIPCHK(c, hipGetLastError());
+  return HBX_OK;
+}
+
+int hbx_rs_encode_ragged_d(hbx_ctx* c, uint8_t* d_buf, uint64_t buf_bytes, const uint64_t* off, const uint32_t* len,
+                           const uint32_t* pitch, uint32_t inst, uint32_t k, uint32_t m, void* stream) {
+  if (!c || !d_buf) return fail(c, HBX_E_INVALID_ARG, "hbx_rs_encode_ragged_d: bad args");
+  if (k == 0 || k > (uint32_t)RS_MAX_K || k + m > (uint32_t)RS_MAX_N)
+    return fail(c, HBX_E_INVALID_ARG, "rs: need 1 <= k <= %d and k + m <= %d (k=%u m=%u)", RS_MAX_K, RS_MAX_N, k, m);
+  uint32_t max_len = 0;
+  int rc = rg_check(c, "hbx_rs_encode_ragged_d", buf_bytes, off, len, pitch, inst, k + m, &max_len);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = pick(c, stream);
+  stream_scope ss_{c, s};
+  if (m == 0) return HBX_OK;  // Coding::Trivial
+  rc = rs_setup(c, k, m, s);
+  if (rc) return rc;
+  const size_t bytes = (size_t)inst * sizeof(rg_desc);
+  uint8_t* h = rg_begin(c, bytes);
+  if (!h) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_rs_encode_ragged_d: descriptor staging");
+  rg_fill(reinterpret_cast<rg_desc*>(h), off, len, pitch, inst);
+  rc = rg_upload(c, bytes, s);
+  if (rc) return rc;
+  rs_code_rg(c, d_buf, c->rg_dev.as<rg_desc>(), max_len, k, inst, c->rs_enc_job.as<rs_job>(),
+             c->rs_enc_ptab.as<gf_ptab>(), 0u, m, s);
+  HIPCHK(c, hipGetLastError());
+  return HBX_OK;
+}
+
+int hbx_rs_reconstruct_ragged_d(hbx_ctx* c, uint8_t* d_buf, uint64_t buf_bytes, const uint64_t* off,
+                                const uint32_t* len, const uint32_t* pitch, const uint8_t* d_present, uint32_t inst,
+                                uint32_t k, uint32_t m, int32_t* d_status, void* stream) {
+  if (!c || !d_buf || !d_present || !d_status) return fail(c, HBX_E_INVALID_ARG, "hbx_rs_reconstruct_ragged_d: bad args");
+  if (k == 0 || k > (uint32_t)RS_MAX_K || k + m > (uint32_t)RS_MAX_N)
+    return fail(c, HBX_E_INVALID_ARG, "rs: need 1 <= k <= %d and k + m <= %d (k=%u m=%u)", RS_MAX_K, RS_MAX_N, k, m);
+  uint32_t max_len = 0;
+  int rc = rg_check(c, "hbx_rs_reconstruct_ragged_d", buf_bytes, off, len, pitch, inst, k + m, &max_len);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = pick(c, stream);
+  stream_scope ss_{c, s};
+  rc = rs_setup(c, k, m, s);
+  if (rc) return rc;
+  const size_t bytes = (size_t)inst * sizeof(rg_desc);
+  uint8_t* h = rg_begin(c, bytes);
+  if (!h) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_rs_reconstruct_ragged_d: descriptor staging");
+  rg_fill(reinterpret_cast<rg_desc*>(h), off, len, pitch, inst);
+  rc = rg_upload(c, bytes, s);
+  if (rc) return rc;
+  return rs_reconstruct_rg(c, d_buf, c->rg_dev.as<rg_desc>(), max_len, d_present, inst, k, m, d_status, s);
+}
+
+int hbx_merkle_build_ragged_d(hbx_ctx* c, const uint8_t* d_buf, uint64_t buf_bytes, const uint64_t* off,
+                              const uint32_t* len, const uint32_t* pitch, uint32_t inst, uint32_t n, uint8_t* d_nodes,
+                              uint8_t* d_roots, void* stream) {
+  if (!c || !d_buf || (!d_nodes && !d_roots)) return fail(c, HBX_E_INVALID_ARG, "hbx_merkle_build_ragged_d: bad args");
+  if (n == 0 || n > (uint32_t)RS_MAX_N) return fail(c, HBX_E_INVALID_ARG, "merkle: need 1 <= n <= 256");
+  uint32_t max_len = 0;
+  int rc = rg_check(c, "hbx_merkle_build_ragged_d", buf_bytes, off, len, pitch, inst, n, &max_len);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = pick(c, stream);
+  stream_scope ss_{c, s};
+  if (!c->leaf_hash.ensure((size_t)inst * n * 32) || (!d_roots && !c->roots.ensure((size_t)inst * 32)))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "merkle: leaf hashes");
+  const size_t bytes = (size_t)inst * sizeof(rg_desc);
+  uint8_t* h = rg_begin(c, bytes);
+  if (!h) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_merkle_build_ragged_d: descriptor staging");
+  rg_fill(reinterpret_cast<rg_desc*>(h), off, len, pitch, inst);
+  rc = rg_upload(c, bytes, s);
+  if (rc) return rc;
+  return merkle_tree_rg(c, d_buf, c->rg_dev.as<rg_desc>(), inst, n, nullptr, 0, true,
+                        d_roots ? d_roots : c->roots.as<uint8_t>(), d_nodes, s);
+}
+
+int hbx_merkle_validate_ragged_d(hbx_ctx* c, const uint8_t* d_values, uint64_t values_bytes, const uint64_t* val_off,
+                                 const uint8_t* d_node_hash, const uint8_t* d_sib_hash, const uint32_t* d_sides,
+                                 const uint32_t* d_depth, const uint8_t* d_root, const uint32_t* d_sender,
+                                 uint32_t count, uint32_t nproofs, uint8_t* d_valid, void* stream) {
+  if (!c || !d_values || !val_off || !d_node_hash || !d_sib_hash || !d_sides || !d_depth || !d_root || !d_sender ||
+      !d_valid || nproofs == 0)
+    return fail(c, HBX_E_INVALID_ARG, "hbx_merkle_validate_ragged_d: bad args");
+  for (uint32_t j = 0; j < nproofs; j++)
+    if (val_off[j + 1] < val_off[j] || val_off[j + 1] - val_off[j] > 0xFFFFFFFFull)
+      return fail(c, HBX_E_INVALID_ARG, "hbx_merkle_validate_ragged_d: val_off[%u..] is not a non-decreasing offset list", j);
+  if (val_off[nproofs] > values_bytes)
+    return fail(c, HBX_E_INVALID_ARG, "hbx_merkle_validate_ragged_d: val_off ends at %llu, past the %llu value bytes",
+                (unsigned long long)val_off[nproofs], (unsigned long long)values_bytes);
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = pick(c, stream);
+  stream_scope ss_{c, s};
+  // long values (more than 256 bytes: Echo proofs of real shards) get their leaf digests from the
+  // leaf kernels, in blocks of one length each: sorted by (length, index), every run of a length is
+  // cut into blocks of B lanes.  The digests land at the proof's own index, so neither the order
+  // of the proofs nor this grouping shows in the results.
+  const uint32_t B = c->merkle == HBX_MERKLE_SHA256 ? 64 : 32;
+  std::vector<uint64_t> lng;  // (length << 32) | index of every long value
+  for (uint32_t j = 0; j < nproofs; j++)
+    if (val_off[j + 1] - val_off[j] > 256) lng.push_back(((val_off[j + 1] - val_off[j]) << 32) | j);
+  if (!std::is_sorted(lng.begin(), lng.end())) std::sort(lng.begin(), lng.end());
+  std::vector<uint32_t> blk_len, blk_idx;
+  blk_idx.reserve(lng.size() + B);
+  for (size_t i = 0; i < lng.size();) {
+    size_t e = i;
+    while (e < lng.size() && e - i < B && (lng[e] >> 32) == (lng[i] >> 32)) e++;
+    blk_len.push_back((uint32_t)(lng[i] >> 32));
+    for (size_t q = 0; q < B; q++) blk_idx.push_back(i + q < e ? (uint32_t)lng[i + q] : VAL_NONE);
+    i = e;
+  }
+  const size_t nblk = blk_len.size();
+  const size_t o_len = (size_t)(nproofs + 1) * 8, o_idx = o_len + ((nblk * 4 + 7) & ~(size_t)7),
+               bytes = o_idx + nblk * B * 4;
+  uint8_t* h = rg_begin(c, bytes);
+  if (!h || (nblk && !c->val_digest.ensure((size_t)nproofs * 32)))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_merkle_validate_ragged_d: out of memory");
+  memcpy(h, val_off, o_len);
+  if (nblk) {
+    memcpy(h + o_len, blk_len.data(), nblk * 4);
+    memcpy(h + o_idx, blk_idx.data(), nblk * B * 4);
+  }
+  int rc = rg_upload(c, bytes, s);
+  if (rc) return rc;
+  const uint8_t* dv = c->rg_dev.as<uint8_t>();
+  const uint64_t* d_off = reinterpret_cast<const uint64_t*>(dv);
+  if (nblk) {
+    timed t_(c, HBX_K_MERKLE_LEAVES, s);
+    if (c->merkle == HBX_MERKLE_SHA256)
+      hipLaunchKernelGGL(k_merkle_values_sha256_rg, dim3((unsigned)nblk), dim3(128), 0, s, d_values, d_off,
+                         reinterpret_cast<const uint32_t*>(dv + o_len), reinterpret_cast<const uint32_t*>(dv + o_idx),
+                         c->val_digest.as<uint32_t>());
+    else
+      hipLaunchKernelGGL(k_merkle_values_sha3_rg, dim3((unsigned)nblk), dim3(64), 0, s, d_values, d_off,
+                         reinterpret_cast<const uint32_t*>(dv + o_len), reinterpret_cast<const uint32_t*>(dv + o_idx),
+                         c->val_digest.as<uint32_t>());
+    HIPCHK(c, hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_merkle_validate_rg, dim3((nproofs + 63) / 64), dim3(64), 0, s, d_values, d_off, d_node_hash,
+                     d_sib_hash, d_sides, d_depth, d_root, d_sender, count, nproofs, d_valid, c->merkle,
+                     c->val_digest.as<uint32_t>());
+  HIPCHK(c, hipGetLastError());
+  return HBX_OK;
+}
+
+int hbx_broadcast_decode_ragged_d(hbx_ctx* c, uint8_t* d_buf, uint64_t buf_bytes, const uint64_t* off,
+                                  const uint32_t* len, const uint32_t* pitch, const uint8_t* d_present,
+                                  const uint8_t* d_leaf_hash, const uint8_t* d_root_expect, uint32_t inst, uint32_t k,
+                                  uint32_t m, uint8_t* d_out, uint64_t out_bytes, const uint64_t* out_off,
+                                  uint64_t* d_out_len, int32_t* d_status, void* stream) {
+  const char* fn = "hbx_broadcast_decode_ragged_d";
+  if (!c || !d_buf || !d_present || !d_root_expect || !d_out || !out_off || !d_out_len || !d_status)
+    return fail(c, HBX_E_INVALID_ARG, "%s: bad args", fn);
+  if (k == 0 || k > (uint32_t)RS_MAX_K || k + m > (uint32_t)RS_MAX_N)
+    return fail(c, HBX_E_INVALID_ARG, "rs: need 1 <= k <= %d and k + m <= %d (k=%u m=%u)", RS_MAX_K, RS_MAX_N, k, m);
+  const uint32_t n = k + m;
+  uint32_t max_len = 0;
+  int rc = rg_check(c, fn, buf_bytes, off, len, pitch, inst, n, &max_len);
+  if (rc) return rc;
+  // the payload length comes from the (untrusted) header: k len - 4 bytes is the most glue_shards
+  // can take, so every instance's output range must hold that many, apart from the others'
+  std::vector<std::pair<uint64_t, uint64_t>> rng;
+  for (uint32_t q = 0; q < inst; q++) {
+    const uint64_t need = (uint64_t)k * len[q] >= 4 ? (uint64_t)k * len[q] - 4 : 0;
+    if (out_off[q] > out_bytes || need > out_bytes - out_off[q])
+      return fail(c, HBX_E_INVALID_ARG, "%s: instance %u: no room for k len - 4 = %llu bytes at out_off %llu of %llu", fn,
+                  q, (unsigned long long)need, (unsigned long long)out_off[q], (unsigned long long)out_bytes);
+    if (need) rng.emplace_back(out_off[q], out_off[q] + need);
+  }
+  std::sort(rng.begin(), rng.end());
+  for (size_t r = 1; r < rng.size(); r++)
+    if (rng[r].first < rng[r - 1].second) return fail(c, HBX_E_INVALID_ARG, "%s: output ranges overlap", fn);
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = pick(c, stream);
+  stream_scope ss_{c, s};
+  rc = rs_setup(c, k, m, s);
+  if (rc) return rc;
+  if (!c->roots.ensure((size_t)inst * 32) || !c->leaf_hash.ensure((size_t)inst * n * 32) ||
+      !c->leaf_slots.ensure((size_t)inst * (m ? m : 1) * 2))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "%s: out of device memory", fn);
+  const size_t o_out = (size_t)inst * sizeof(rg_desc), bytes = o_out + (size_t)inst * 8;
+  uint8_t* h = rg_begin(c, bytes);
+  if (!h) return fail(c, HBX_E_OUT_OF_MEMORY, "%s: descriptor staging", fn);
+  rg_fill(reinterpret_cast<rg_desc*>(h), off, len, pitch, inst);
+  memcpy(h + o_out, out_off, (size_t)inst * 8);
+  rc = rg_upload(c, bytes, s);
+  if (rc) return rc;
+  const rg_desc* d_desc = c->rg_dev.as<rg_desc>();
+  rc = rs_reconstruct_rg(c, d_buf, d_desc, max_len, d_present, inst, k, m, d_status, s);
+  if (rc) return rc;
+  if (d_leaf_hash) {
+    const uint32_t words = inst * n * 8;
+    hipLaunchKernelGGL(k_import_leaf_hashes, dim3((words + 255) / 256), dim3(256), 0, s, d_leaf_hash, d_present,
+                       inst * n, c->leaf_hash.as<uint32_t>());
+    if (m)  // Coding::Trivial reconstructs nothing
+      hipLaunchKernelGGL(k_missing_slots, dim3(inst), dim3(64), 0, s, d_present, n, d_status, m,
+                         c->leaf_slots.as<uint16_t>());
+    HIPCHK(c, hipGetLastError());
+    rc = merkle_tree_rg(c, d_buf, d_desc, inst, n, c->leaf_slots.as<uint16_t>(), m, m != 0, c->roots.as<uint8_t>(),
+                        nullptr, s);
+  } else {
+    rc = merkle_tree_rg(c, d_buf, d_desc, inst, n, nullptr, 0, true, c->roots.as<uint8_t>(), nullptr, s);
+  }
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_root_check, dim3((inst + 63) / 64), dim3(64), 0, s, c->roots.as<uint8_t>(), d_root_expect, inst,
+                     d_status);
+  const uint64_t glue_blocks = ((uint64_t)k * max_len + 4095) / 4096;
+  hipLaunchKernelGGL(k_glue_rg, dim3((unsigned)glue_blocks, inst), dim3(256), 0, s, d_buf, d_desc, k, d_out,
+                     reinterpret_cast<const uint64_t*>(c->rg_dev.as<uint8_t>() + o_out), d_out_len, d_status);
+  HIPCHK(c, hipGetLastError());
+  return HBX_OK;
 }
 
 // ---- Broadcast, host-pointer forms (include/hbx.h): the _d calls above on context-owned staging

@@ -98,6 +98,11 @@ EXPORTS = (
     "hbx_set_batch_verify",
     "hbx_get_batch_stats",
     "hbx_get_batch_sums",
+    "hbx_rs_encode_ragged_d",
+    "hbx_rs_reconstruct_ragged_d",
+    "hbx_merkle_build_ragged_d",
+    "hbx_merkle_validate_ragged_d",
+    "hbx_broadcast_decode_ragged_d",
 )
 
 DIGEST_SHA256 = 0
@@ -227,6 +232,15 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         u32p = ctypes.POINTER(ctypes.c_uint32)
         lib.hbx_get_batch_stats.argtypes = [P, u32p, u32p, u32p]
         lib.hbx_get_batch_sums.argtypes = [P, u8p, ctypes.c_size_t]
+    # ragged Broadcast calls (per-instance shard lengths): absent from a library built before them
+    # (tools/bench_broadcast_ragged.py --lib times such a build through the uniform calls)
+    if hasattr(lib, "hbx_rs_encode_ragged_d"):
+        u64 = ctypes.c_uint64
+        lib.hbx_rs_encode_ragged_d.argtypes = [P, P, u64, P, P, P, u32, u32, u32, P]
+        lib.hbx_rs_reconstruct_ragged_d.argtypes = [P, P, u64, P, P, P, P, u32, u32, u32, P, P]
+        lib.hbx_merkle_build_ragged_d.argtypes = [P, P, u64, P, P, P, u32, u32, P, P, P]
+        lib.hbx_merkle_validate_ragged_d.argtypes = [P, P, u64, P, P, P, P, P, P, P, u32, u32, P, P]
+        lib.hbx_broadcast_decode_ragged_d.argtypes = [P, P, u64, P, P, P, P, P, P, u32, u32, u32, P, u64, P, P, P, P]
     _lib = lib
     return lib
 
@@ -245,6 +259,21 @@ def build_info() -> dict:
 
 def _u8(a: np.ndarray):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+
+
+def ragged_layout(lens, n: int, align: int = 16):
+    """A ragged Broadcast buffer for shard lengths ``lens`` with ``n`` rows per instance, instances
+    back to back: -> (off uint64[inst], pitch uint32[inst], total_bytes).  pitch = len rounded up to
+    ``align`` (a multiple of 4), so every row -- and every instance -- starts ``align``-aligned."""
+    if align <= 0 or align % 4:
+        raise ValueError(f"ragged_layout: align {align} must be a positive multiple of 4")
+    lens = np.asarray(lens, dtype=np.int64).reshape(-1)
+    if n < 1 or lens.size == 0 or (lens < 1).any() or (lens > 0xFFFFFFFF - align).any():
+        raise ValueError("ragged_layout: need n >= 1 and shard lengths in [1, 2^32 - align)")
+    pitch = (lens + align - 1) // align * align
+    size = pitch * n
+    off = np.concatenate(([0], np.cumsum(size)[:-1]))
+    return off.astype(np.uint64), pitch.astype(np.uint32), int(size.sum())
 
 
 def pack_bits(bools) -> np.ndarray:
@@ -874,6 +903,106 @@ class Context:
         self._check(self.lib.hbx_broadcast_decode_leaves_d(
             self.h, d_shards.data_ptr(), d_present.data_ptr(), d_leaf_hash.data_ptr(), d_root.data_ptr(), inst, k, m,
             L, d_out.data_ptr(), d_out.shape[1], d_out_len.data_ptr(), d_status.data_ptr(), self._stream(stream)))
+
+    # -- Broadcast, ragged forms: per-instance shard lengths in one call ----------------------------
+    ragged_layout = staticmethod(ragged_layout)
+
+    @staticmethod
+    def _ragged_desc(what: str, buf_bytes: int, off, lens, pitch, n: int):
+        """The descriptor rules of include/hbx.h, checked before the library is reached."""
+        off = np.ascontiguousarray(off, dtype=np.uint64).reshape(-1)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32).reshape(-1)
+        pitch = np.ascontiguousarray(pitch, dtype=np.uint32).reshape(-1)
+        inst = off.size
+        if inst == 0 or lens.size != inst or pitch.size != inst or n < 1:
+            raise ValueError(f"{what}: off, len and pitch need one entry per instance (and n >= 1)")
+        if (off % 4).any() or (pitch % 4).any():
+            raise ValueError(f"{what}: off and pitch must be multiples of 4")
+        if (lens == 0).any() or (pitch < lens).any():
+            raise ValueError(f"{what}: need pitch >= len >= 1 for every instance")
+        o, end = off.astype(object), off.astype(object) + pitch.astype(object) * n
+        if (end > buf_bytes).any():
+            raise ValueError(f"{what}: an instance's rows end past the buffer ({buf_bytes} bytes)")
+        order = np.argsort(off, kind="stable")
+        for a, b in zip(order[:-1], order[1:]):
+            if o[b] < end[a]:
+                raise ValueError(f"{what}: instances {a} and {b} overlap")
+        return off, lens, pitch, inst
+
+    @staticmethod
+    def _flat_u8(what: str, t):
+        if t.dim() != 1 or t.element_size() != 1 or not t.is_contiguous():
+            raise ValueError(f"{what}: need a contiguous 1-D byte tensor")
+        return t.numel()
+
+    def rs_encode_ragged_d(self, d_buf, off, lens, pitch, k: int, m: int, stream=None):
+        """hbx_rs_encode_ragged_d: d_buf uint8[buf_bytes]; off / lens / pitch host arrays [inst]."""
+        nb = self._flat_u8("rs_encode_ragged_d", d_buf)
+        off, lens, pitch, inst = self._ragged_desc("rs_encode_ragged_d", nb, off, lens, pitch, k + m)
+        self._check(self.lib.hbx_rs_encode_ragged_d(self.h, d_buf.data_ptr(), nb, off.ctypes.data, lens.ctypes.data,
+                                                    pitch.ctypes.data, inst, k, m, self._stream(stream)))
+
+    def rs_reconstruct_ragged_d(self, d_buf, off, lens, pitch, d_present, d_status, k: int, m: int, stream=None):
+        nb = self._flat_u8("rs_reconstruct_ragged_d", d_buf)
+        off, lens, pitch, inst = self._ragged_desc("rs_reconstruct_ragged_d", nb, off, lens, pitch, k + m)
+        if tuple(d_present.shape) != (inst, k + m) or d_status.numel() != inst:
+            raise ValueError(f"rs_reconstruct_ragged_d: d_present must be [{inst}, {k + m}] and d_status [{inst}]")
+        self._check(self.lib.hbx_rs_reconstruct_ragged_d(
+            self.h, d_buf.data_ptr(), nb, off.ctypes.data, lens.ctypes.data, pitch.ctypes.data, d_present.data_ptr(),
+            inst, k, m, d_status.data_ptr(), self._stream(stream)))
+
+    def merkle_build_ragged_d(self, d_buf, off, lens, pitch, n: int, d_nodes=None, d_roots=None, stream=None):
+        """hbx_merkle_build_ragged_d: d_nodes uint8[inst, node_count(n), 32] and / or d_roots uint8[inst, 32]."""
+        nb = self._flat_u8("merkle_build_ragged_d", d_buf)
+        off, lens, pitch, inst = self._ragged_desc("merkle_build_ragged_d", nb, off, lens, pitch, n)
+        if d_nodes is None and d_roots is None:
+            raise ValueError("merkle_build_ragged_d: give d_nodes or d_roots")
+        self._check(self.lib.hbx_merkle_build_ragged_d(
+            self.h, d_buf.data_ptr(), nb, off.ctypes.data, lens.ctypes.data, pitch.ctypes.data, inst, n,
+            None if d_nodes is None else d_nodes.data_ptr(), None if d_roots is None else d_roots.data_ptr(),
+            self._stream(stream)))
+
+    def merkle_validate_ragged_d(self, d_values, val_off, d_nodes, d_sibs, d_sides, d_depth, d_root, d_sender,
+                                 count: int, d_valid, stream=None):
+        """hbx_merkle_validate_ragged_d: value j = d_values[val_off[j] : val_off[j + 1]] (val_off: host
+        uint64[nproofs + 1]); the other arrays as merkle_validate_d."""
+        nb = self._flat_u8("merkle_validate_ragged_d", d_values)
+        nproofs = d_valid.numel()
+        val_off = np.ascontiguousarray(val_off, dtype=np.uint64).reshape(-1)
+        if nproofs == 0 or val_off.size != nproofs + 1:
+            raise ValueError(f"merkle_validate_ragged_d: val_off needs nproofs + 1 = {nproofs + 1} entries, got {val_off.size}")
+        if (val_off[1:] < val_off[:-1]).any() or int(val_off[-1]) > nb:
+            raise ValueError("merkle_validate_ragged_d: val_off must be non-decreasing and end within d_values")
+        self._check(self.lib.hbx_merkle_validate_ragged_d(
+            self.h, d_values.data_ptr(), nb, val_off.ctypes.data, d_nodes.data_ptr(), d_sibs.data_ptr(),
+            d_sides.data_ptr(), d_depth.data_ptr(), d_root.data_ptr(), d_sender.data_ptr(), count, nproofs,
+            d_valid.data_ptr(), self._stream(stream)))
+
+    def broadcast_decode_ragged_d(self, d_buf, off, lens, pitch, d_present, d_root, k: int, m: int, d_out, out_off,
+                                  d_out_len, d_status, d_leaf_hash=None, stream=None):
+        """hbx_broadcast_decode_ragged_d: instance q's payload at d_out[out_off[q]:] (out_off: host
+        uint64[inst]); with d_leaf_hash uint8[inst, k + m, 32] only reconstructed shards are hashed."""
+        nb = self._flat_u8("broadcast_decode_ragged_d", d_buf)
+        ob = self._flat_u8("broadcast_decode_ragged_d", d_out)
+        n = k + m
+        off, lens, pitch, inst = self._ragged_desc("broadcast_decode_ragged_d", nb, off, lens, pitch, n)
+        out_off = np.ascontiguousarray(out_off, dtype=np.uint64).reshape(-1)
+        if out_off.size != inst or tuple(d_present.shape) != (inst, n) or d_status.numel() != inst \
+                or d_out_len.numel() != inst or d_root.numel() != inst * 32:
+            raise ValueError(f"broadcast_decode_ragged_d: out_off, d_present, d_root, d_out_len and d_status need {inst} "
+                             f"instances of {n} shards")
+        spans = sorted((int(o), int(o) + max(k * int(ln) - 4, 0)) for o, ln in zip(out_off, lens))
+        if any(e > ob for _, e in spans):
+            raise ValueError("broadcast_decode_ragged_d: an instance has no room for k * len - 4 bytes in d_out")
+        if any(b[0] < a[1] for a, b in zip(spans[:-1], spans[1:]) if b[1] > b[0] and a[1] > a[0]):
+            raise ValueError("broadcast_decode_ragged_d: output ranges overlap")
+        if d_leaf_hash is not None and (tuple(d_leaf_hash.shape) != (inst, n, 32) or d_leaf_hash.element_size() != 1
+                                        or not d_leaf_hash.is_contiguous()):
+            raise ValueError(f"broadcast_decode_ragged_d: d_leaf_hash must be contiguous uint8[{inst}, {n}, 32]")
+        self._check(self.lib.hbx_broadcast_decode_ragged_d(
+            self.h, d_buf.data_ptr(), nb, off.ctypes.data, lens.ctypes.data, pitch.ctypes.data, d_present.data_ptr(),
+            None if d_leaf_hash is None else d_leaf_hash.data_ptr(), d_root.data_ptr(), inst, k, m, d_out.data_ptr(), ob,
+            out_off.ctypes.data, d_out_len.data_ptr(), d_status.data_ptr(), self._stream(stream)))
 
     def get_ct_valid_d(self, d_ct_valid, stream=None):
         self._check(self.lib.hbx_get_ct_valid_d(self.h, d_ct_valid.data_ptr(), self._stream(stream)))

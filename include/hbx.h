@@ -503,6 +503,63 @@ int hbx_broadcast_decode_leaves_d(hbx_ctx* ctx, uint8_t* d_shards, const uint8_t
                                   uint32_t k, uint32_t m, uint32_t L, uint8_t* d_out, uint64_t out_stride,
                                   uint64_t* d_out_len, int32_t* d_status, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Broadcast, ragged forms: per-instance shard lengths in one call.  Each proposer frames its own
+ * contribution with shard_len = ceil((len + 4) / (N - 2f)) (src/broadcast.rs:341-353), so the N
+ * instances at one node have N shard lengths; these calls take them all at once.
+ *
+ * Layout: one device byte buffer d_buf[buf_bytes] holds every instance.  Instance q is described
+ * by three HOST arrays of `inst` entries: off[q] (byte offset of its row 0), len[q] (its shard
+ * length, >= 1) and pitch[q] (its row pitch, >= len[q]); row i (i < k + m) is at
+ * off[q] + i * pitch[q].  Required, else HBX_E_INVALID_ARG before anything is launched:
+ * off[q] % 4 == 0, pitch[q] % 4 == 0, pitch[q] >= len[q] >= 1, off[q] + (k + m) * pitch[q] <=
+ * buf_bytes, and no two instances' ranges overlap.  The host arrays (val_off and out_off below
+ * too) are consumed before the call returns.  Pad bytes [len, pitch) of a row are never part of a
+ * result: they may hold anything, and their content after a call is unspecified; no byte outside
+ * [off[q], off[q] + (k + m) * pitch[q]) of any instance is written.  Rows are dword rows whatever
+ * their length, so every length runs the byte-permute coding kernel.  Device pointers,
+ * stream-ordered; k + m <= 256, k <= 128, one (k, m) per call.
+ *
+ * hbx_rs_encode_ragged_d -- Coding::encode (src/broadcast.rs:632-640, called at :365) for every
+ *   instance; m == 0 is a no-op.
+ * hbx_rs_reconstruct_ragged_d -- Coding::reconstruct_shards (src/broadcast.rs:643-657, called at
+ *   :667): d_present[inst][k + m]; d_status[inst] HBX_OK or HBX_E_TOO_FEW_SHARDS.
+ * hbx_merkle_build_ragged_d -- MerkleTree::from_vec (src/broadcast.rs:381) over the leaves
+ *   [i] || row i's len[q] bytes: d_nodes[inst][hbx_merkle_node_count(n)][32] and d_roots[inst][32],
+ *   either may be NULL (not both); both HBX_MERKLE_* variants.  The nodes feed hbx_merkle_proofs_d.
+ * hbx_merkle_validate_ragged_d -- Broadcast::validate_proof (src/broadcast.rs:555-575) for values
+ *   of any lengths in one call: value j is d_values[val_off[j] .. val_off[j + 1]) (val_off: HOST
+ *   array of nproofs + 1 non-decreasing offsets, val_off[nproofs] <= values_bytes); the other
+ *   arrays as hbx_merkle_validate_d.  A zero-length value is invalid (d_valid[j] = 0), not an
+ *   error.  The results do not depend on the order of the proofs.
+ * hbx_broadcast_decode_ragged_d -- decode_from_shards + glue_shards (src/broadcast.rs:660-707) per
+ *   instance, statuses as hbx_broadcast_decode_d.  Instance q's payload is written at
+ *   d_out + out_off[q] (HOST array); each instance needs room for k * len[q] - 4 bytes there
+ *   whenever k * len[q] >= 4 (within out_bytes, apart from the other instances' room), else
+ *   HBX_E_INVALID_ARG; no other byte of d_out is written.  d_leaf_hash[inst][k + m][32] may be
+ *   NULL; given, it is the leaf-sharing decode of hbx_broadcast_decode_leaves_d (only
+ *   reconstructed shards are hashed).
+ * ------------------------------------------------------------------------------------------- */
+int hbx_rs_encode_ragged_d(hbx_ctx* ctx, uint8_t* d_buf, uint64_t buf_bytes, const uint64_t* off,
+                           const uint32_t* len, const uint32_t* pitch, uint32_t inst, uint32_t k, uint32_t m,
+                           void* stream);
+int hbx_rs_reconstruct_ragged_d(hbx_ctx* ctx, uint8_t* d_buf, uint64_t buf_bytes, const uint64_t* off,
+                                const uint32_t* len, const uint32_t* pitch, const uint8_t* d_present,
+                                uint32_t inst, uint32_t k, uint32_t m, int32_t* d_status, void* stream);
+int hbx_merkle_build_ragged_d(hbx_ctx* ctx, const uint8_t* d_buf, uint64_t buf_bytes, const uint64_t* off,
+                              const uint32_t* len, const uint32_t* pitch, uint32_t inst, uint32_t n,
+                              uint8_t* d_nodes, uint8_t* d_roots, void* stream);
+int hbx_merkle_validate_ragged_d(hbx_ctx* ctx, const uint8_t* d_values, uint64_t values_bytes,
+                                 const uint64_t* val_off, const uint8_t* d_node_hash, const uint8_t* d_sib_hash,
+                                 const uint32_t* d_sides, const uint32_t* d_depth, const uint8_t* d_root,
+                                 const uint32_t* d_sender, uint32_t count, uint32_t nproofs, uint8_t* d_valid,
+                                 void* stream);
+int hbx_broadcast_decode_ragged_d(hbx_ctx* ctx, uint8_t* d_buf, uint64_t buf_bytes, const uint64_t* off,
+                                  const uint32_t* len, const uint32_t* pitch, const uint8_t* d_present,
+                                  const uint8_t* d_leaf_hash, const uint8_t* d_root_expect, uint32_t inst,
+                                  uint32_t k, uint32_t m, uint8_t* d_out, uint64_t out_bytes,
+                                  const uint64_t* out_off, uint64_t* d_out_len, int32_t* d_status, void* stream);
+
 /* Host-pointer forms of the Broadcast calls: the same operations and layouts on HOST buffers,
  * staged through device buffers the context owns, on the context's own stream; they block until
  * the outputs are back (the stack-A/B convention above).  What a thin Rust FFI calls from
