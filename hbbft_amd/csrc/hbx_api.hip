@@ -67,6 +67,8 @@ struct hbx_ctx {
   int combine_lanes = 0;              // hbx_set_combine_lanes: 0 auto, 1 or 4 lanes per Lagrange term
   int coin_lanes_used = 0;            // lanes per check of the last signature-share launch
   int lanes_used = 0;                 // lanes per check of the last share-check launch
+  int ct_check = HBX_CT_CHECK_WIDE;   // hbx_set_ct_check: Ciphertext::verify of hbx_sk_decrypt
+  int ct_check_used = -1;             // the mode the last hbx_sk_decrypt ran (-1: none yet)
   // era state
   uint32_t n_keys = 0;
   dbuf comb_partial, comb_done;  // k_combine_q: per-block partial sums, per-proposer block counters
@@ -100,10 +102,11 @@ struct hbx_ctx {
   uint32_t batch_last_p = 0;
   dbuf b_seed, b_AJ, b_T, b_C, b_Asum, b_A, b_B, b_cls0, b_cand, b_pass, b_zero, b_cls, b_ctok, b_stats;
   // u32 counters of the checks the fallback path decided: one for the one-lane decryption-share
-  // checks, one for the two-lane coin checks (launches of the two kinds on different streams must
-  // not mix their counts); fb_last names the counter of the last share-check launch of either kind,
-  // or none when that launch used a lane count without a fallback path
-  dbuf fb_lanes, fb_coin;
+  // checks, one for the two-lane coin checks, one for the pair-lane ciphertext checks of
+  // hbx_sk_decrypt, summed over the call's chunks (launches of different kinds on different streams
+  // must not mix their counts); fb_last names the counter of the last launch of any kind, or none
+  // when that launch used a lane count without a fallback path
+  dbuf fb_lanes, fb_coin, fb_ct;
   dbuf* fb_last = nullptr;
   dbuf hs[6];                   // staging of the host-pointer broadcast calls
   // combine state
@@ -632,7 +635,7 @@ int hbx_ctx_destroy(hbx_ctx* c) {
                   &c->coin_comb_st, &c->coin_mpk_comp, &c->coin_mpk, &c->coin_mpk_st, &c->coin_ok, &c->coin_par,
                   &c->coin_out96, &c->dec_st, &c->own_sk, &c->own_S, &c->own_part, &c->lines_d,
                   &c->vs_pk, &c->vs_lines_d, &c->coin_lines_d, &c->vs_blob, &c->vs_off, &c->vs_H, &c->vs_lines, &c->vs_scratch, &c->vs_sig96,
-                  &c->vs_sig, &c->vs_sig_st, &c->vs_status, &c->fe1slot, &c->fb_lanes, &c->fb_coin, &c->hs[0], &c->hs[1], &c->hs[2], &c->hs[3], &c->hs[4], &c->hs[5], &c->coin_use, &c->bv_commit48, &c->bv_C, &c->bv_cst, &c->bv_rows,
+                  &c->vs_sig, &c->vs_sig_st, &c->vs_status, &c->fe1slot, &c->fb_lanes, &c->fb_coin, &c->fb_ct, &c->hs[0], &c->hs[1], &c->hs[2], &c->hs[3], &c->hs[4], &c->hs[5], &c->coin_use, &c->bv_commit48, &c->bv_C, &c->bv_cst, &c->bv_rows,
                   &c->bv_rows48, &c->bv_pst, &c->bv_ackp, &c->bv_acky, &c->bv_vals, &c->bv_out,
                   &c->kg_sk, &c->kg_out, &c->kg_st, &c->b_seed, &c->b_AJ, &c->b_T, &c->b_C, &c->b_Asum, &c->b_A, &c->b_B,
                   &c->b_cls0, &c->b_cand, &c->b_pass, &c->b_zero, &c->b_cls, &c->b_ctok, &c->b_stats, &c->rg_dev};
@@ -667,6 +670,15 @@ int hbx_set_verify_lanes(hbx_ctx* c, int lanes) {
 }
 
 int hbx_get_verify_lanes_used(const hbx_ctx* c) { return c ? c->lanes_used : 0; }
+
+int hbx_set_ct_check(hbx_ctx* c, int mode) {
+  if (!c || (mode != HBX_CT_CHECK_WIDE && mode != HBX_CT_CHECK_PAIR))
+    return fail(c, HBX_E_INVALID_ARG, "hbx_set_ct_check: 0 (wide) or 1 (pair), not %d", mode);
+  c->ct_check = mode;
+  return HBX_OK;
+}
+
+int hbx_get_ct_check_used(const hbx_ctx* c) { return c ? c->ct_check_used : -1; }
 
 int hbx_debug_force_fallback(hbx_ctx* c, uint32_t every) {
   if (!c) return HBX_E_INVALID_ARG;
@@ -818,28 +830,16 @@ int hbx_set_own_share(hbx_ctx* c, uint32_t me, const uint8_t* sk32) {
   return HBX_OK;
 }
 
-// Ciphertext preparation; with `early_shares` (the fused epoch call) the received shares of the
-// epoch are decoded in the same launch, in waves beside the hash chains.
-static int prepare_impl(hbx_ctx* c, const uint8_t* d_u_comp, const uint8_t* d_v_blob, const uint64_t* d_v_off,
-                        const uint8_t* d_w_comp, uint32_t p, uint64_t max_v_len, uint8_t* d_ct_valid,
-                        void* stream, const uint8_t* early_shares, uint32_t early_n) {
-  if (!c || p == 0 || !d_u_comp || !d_v_off || !d_w_comp)
-    return fail(c, HBX_E_INVALID_ARG, "hbx_prepare_ciphertexts_d: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, stream);
-  stream_scope ss_{c, s};
-  if (!c->U.ensure((size_t)p * sizeof(g1a)) || !c->G2pts.ensure((size_t)2 * p * sizeof(g2a)) || !c->Hj.ensure((size_t)p * sizeof(g2j)) ||
-      !c->lines.ensure((size_t)p * sizeof(line_block)) || !c->lines_d.ensure((size_t)p * sizeof(line_block_d)) ||
-      !c->scratch.ensure((size_t)2 * p * MILLER_LINES * sizeof(fq2d)) || !c->ct_ok.ensure(p) ||
-      !c->ct_valid.ensure(p) || !c->dec_st.ensure((size_t)2 * p * 4))
-    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_prepare_ciphertexts_d: out of device memory");
-  const size_t m_early = early_shares ? (size_t)early_n * p : 0;
-  if (m_early && (!c->S.ensure(m_early * sizeof(g1a)) || !c->S_status.ensure(m_early * 4)))
-    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_prepare_ciphertexts_d: out of device memory");
+// The k_prepare_ct launch: the hash groups (H'_j, Jacobian, into Hj), the decode of U_j and W_j
+// (U, G2pts, dec_st) and, in own-share mode, the halves of sk_me U_j; with `early_shares` the epoch's
+// received shares are decoded beside them.  The caller has sized U, G2pts, Hj and dec_st for p
+// ciphertexts (and S / S_status for the early shares).  Shared by prepare_impl and the pair-lane
+// Ciphertext::verify of hbx_sk_decrypt, which needs none of prepare_impl's line tables.
+static int launch_prepare_ct(hbx_ctx* c, hipStream_t s, const uint8_t* d_u_comp, const uint8_t* d_v_blob,
+                             const uint64_t* d_v_off, const uint8_t* d_w_comp, uint32_t p, const uint8_t* early_shares,
+                             size_t m_early, uint32_t early_n, uint32_t me_early) {
   const dim3 b64(64);
   const bool own = c->own_me != UINT32_MAX;
-  // own entry of the early-decoded matrix (written by k_prepare_lines), as hbx_verify_dec_shares_d
-  const uint32_t me_early = (own && c->own_me < early_n) ? c->own_me : UINT32_MAX;
   {
     timed t_(c, HBX_K_PREPARE_CT, s);
     const uint32_t hash_blocks = (uint32_t)(((size_t)p * HASH_K + 63) / 64);
@@ -864,6 +864,33 @@ static int prepare_impl(hbx_ctx* c, const uint8_t* d_u_comp, const uint8_t* d_v_
     c->own_ready = own;
   }
   HIPCHK(c, hipGetLastError());
+  return HBX_OK;
+}
+
+// Ciphertext preparation; with `early_shares` (the fused epoch call) the received shares of the
+// epoch are decoded in the same launch, in waves beside the hash chains.
+static int prepare_impl(hbx_ctx* c, const uint8_t* d_u_comp, const uint8_t* d_v_blob, const uint64_t* d_v_off,
+                        const uint8_t* d_w_comp, uint32_t p, uint64_t max_v_len, uint8_t* d_ct_valid,
+                        void* stream, const uint8_t* early_shares, uint32_t early_n) {
+  if (!c || p == 0 || !d_u_comp || !d_v_off || !d_w_comp)
+    return fail(c, HBX_E_INVALID_ARG, "hbx_prepare_ciphertexts_d: bad args");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = pick(c, stream);
+  stream_scope ss_{c, s};
+  if (!c->U.ensure((size_t)p * sizeof(g1a)) || !c->G2pts.ensure((size_t)2 * p * sizeof(g2a)) || !c->Hj.ensure((size_t)p * sizeof(g2j)) ||
+      !c->lines.ensure((size_t)p * sizeof(line_block)) || !c->lines_d.ensure((size_t)p * sizeof(line_block_d)) ||
+      !c->scratch.ensure((size_t)2 * p * MILLER_LINES * sizeof(fq2d)) || !c->ct_ok.ensure(p) ||
+      !c->ct_valid.ensure(p) || !c->dec_st.ensure((size_t)2 * p * 4))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_prepare_ciphertexts_d: out of device memory");
+  const size_t m_early = early_shares ? (size_t)early_n * p : 0;
+  if (m_early && (!c->S.ensure(m_early * sizeof(g1a)) || !c->S_status.ensure(m_early * 4)))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_prepare_ciphertexts_d: out of device memory");
+  const dim3 b64(64);
+  const bool own = c->own_me != UINT32_MAX;
+  // own entry of the early-decoded matrix (written by k_prepare_lines), as hbx_verify_dec_shares_d
+  const uint32_t me_early = (own && c->own_me < early_n) ? c->own_me : UINT32_MAX;
+  if (int rc = launch_prepare_ct(c, s, d_u_comp, d_v_blob, d_v_off, d_w_comp, p, early_shares, m_early, early_n, me_early))
+    return rc;
   {
     timed t_(c, HBX_K_PREPARE_LINES, s);
     const uint32_t line_blocks = (2 * p * LINE_K + 63) / 64, own_blocks = own ? (p + 63) / 64 : 0;
@@ -2504,6 +2531,11 @@ struct kg_tmp : dbuf {
 // run faster: the wide check gives a ciphertext-only job a whole 128-thread block (one 16-lane group
 // of its eight busy) and 45 KiB of LDS, so about 768 blocks are resident at a time.
 constexpr uint32_t SK_DECRYPT_CHUNK = 1024;
+// Ciphertexts per pass in HBX_CT_CHECK_PAIR mode (hbbft_amd/hbx.py SK_DECRYPT_PAIR_CHUNK is the same
+// number).  The state is about 2 KiB per ciphertext (U, W and H' decoded, the Jacobian H', and the
+// pair's 1.25 KiB slot for the halves of f): 16,384 ciphertexts are about 35 MB, 512 pair-check
+// waves (one wave per SIMD resident: two full-chip rounds) and 4,096 hash waves.
+constexpr uint32_t SK_DECRYPT_PAIR_CHUNK = 16384;
 
 void be32_to_limbs(const uint8_t* b, uint32_t* k8) {
   for (int q = 0; q < 8; q++)
@@ -2582,22 +2614,63 @@ int hbx_sk_decrypt(hbx_ctx* c, const uint8_t* sk32, const uint8_t* u48, const ui
   HIPCHK(c, hipMemcpyAsync(c->v_off_own.p, v_off, (size_t)(count + 1) * 8, hipMemcpyHostToDevice, s));
   if (total) HIPCHK(c, hipMemcpyAsync(c->v_blob_own.p, v_blob, total, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemsetAsync(c->kg_out.p, 0, total ? total : 16, s));
-  // Ciphertext::verify through the prepared-ciphertext path with its immediate checks, a chunk at a
-  // time.  `sk32` is the node's individual key, not its threshold share: own-share mode is off for
-  // these prepares and restored below; the epoch's prepared ciphertexts are void afterwards.
+  // Ciphertext::verify, a chunk at a time: through the prepared-ciphertext path with its immediate
+  // checks (the wide executor), or, in HBX_CT_CHECK_PAIR mode, k_prepare_ct alone and one lane pair per
+  // ciphertext, without the line tables.  `sk32` is the node's individual key, not its threshold share:
+  // own-share mode is off for these prepares and restored below; the epoch's prepared ciphertexts
+  // are void afterwards.
+  const bool pair = c->ct_check == HBX_CT_CHECK_PAIR;
+  c->ct_check_used = c->ct_check;
+  const uint32_t chunk = pair ? SK_DECRYPT_PAIR_CHUNK : SK_DECRYPT_CHUNK;
+  if (pair) {
+    const size_t cap = std::min(chunk, count);
+    if (!c->U.ensure(cap * sizeof(g1a)) || !c->G2pts.ensure(2 * cap * sizeof(g2a)) || !c->Hj.ensure(cap * sizeof(g2j)) ||
+        !c->dec_st.ensure(2 * cap * 4) || !c->gslot.ensure((cap + 31) / 32 * 64 * 2 * LDS_FQ6D_PACKED * 4) ||
+        !c->fb_ct.ensure(4))
+      return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_sk_decrypt: out of device memory");
+    HIPCHK(c, hipMemsetAsync(c->fb_ct.p, 0, 4, s));
+    c->fb_last = &c->fb_ct;
+  }
   const uint32_t saved_me = c->own_me;
   c->own_me = UINT32_MAX;
   int rc = HBX_OK;
-  for (uint32_t j0 = 0; j0 < count && rc == HBX_OK; j0 += SK_DECRYPT_CHUNK) {
-    const uint32_t m = std::min(SK_DECRYPT_CHUNK, count - j0);
-    rc = prepare_impl(c, c->u_comp_own.as<uint8_t>() + (size_t)j0 * 48, c->v_blob_own.as<uint8_t>(),
-                      c->v_off_own.as<uint64_t>() + j0, c->w_comp_own.as<uint8_t>() + (size_t)j0 * 96, m, maxv,
-                      c->kg_st.as<uint8_t>() + j0, s, nullptr, 0);  // the chunk's HBX_CT_* land in kg_st
+  for (uint32_t j0 = 0; j0 < count && rc == HBX_OK; j0 += chunk) {
+    const uint32_t m = std::min(chunk, count - j0);
+    uint8_t* st = c->kg_st.as<uint8_t>() + j0;  // the chunk's HBX_CT_* land in kg_st
+    if (pair) {
+      rc = launch_prepare_ct(c, s, c->u_comp_own.as<uint8_t>() + (size_t)j0 * 48, c->v_blob_own.as<uint8_t>(),
+                             c->v_off_own.as<uint64_t>() + j0, c->w_comp_own.as<uint8_t>() + (size_t)j0 * 96, m, nullptr, 0,
+                             0, UINT32_MAX);
+      if (rc) break;
+      timed t_(c, HBX_K_CT_CHECKS, s);
+      const dim3 grid((m + 31) / 32);
+      // Miller loops; the final exponentiation with compressed runs; then the pairs whose
+      // decompression met g3 = 0 (SHARE_FALLBACK) once more with Granger-Scott squarings only
+      // (verify_sig_impl's protocol; both retry launches return at once per pair when there are none)
+      for (uint32_t retry = 0; retry < 2; retry++) {
+        hipLaunchKernelGGL(k_verify_ct2, grid, dim3(64), 0, s, c->U.as<g1a>(), c->G2pts.as<g2a>(), c->Hj.as<g2j>(),
+                           c->dec_st.as<int32_t>(), m, st, c->gslot.as<uint32_t>(), retry);
+        if (retry == 0)
+          hipLaunchKernelGGL(k_verify_sig_shares2_fe<true>, grid, dim3(64), 0, s, m, st, c->gslot.as<uint32_t>(),
+                             c->force_fallback, c->fb_ct.as<uint32_t>());
+        else
+          hipLaunchKernelGGL(k_verify_sig_shares2_fe<false>, grid, dim3(64), 0, s, m, st, c->gslot.as<uint32_t>(), 0u,
+                             c->fb_ct.as<uint32_t>());
+      }
+    } else {
+      rc = prepare_impl(c, c->u_comp_own.as<uint8_t>() + (size_t)j0 * 48, c->v_blob_own.as<uint8_t>(),
+                        c->v_off_own.as<uint64_t>() + j0, c->w_comp_own.as<uint8_t>() + (size_t)j0 * 96, m, maxv, st, s,
+                        nullptr, 0);
+    }
     if (rc) break;
+    if (hipGetLastError() != hipSuccess) {
+      rc = fail(c, HBX_E_DEVICE, "hbx_sk_decrypt: device error");
+      break;
+    }
     {
       timed t_(c, HBX_K_SK_DECRYPT, s);
       hipLaunchKernelGGL(k_sk_decrypt, dim3((m + 63) / 64), dim3(64), 0, s, c->U.as<g1a>(),
-                         c->kg_st.as<uint8_t>() + j0, c->kg_sk.as<uint32_t>(), c->v_blob_own.as<uint8_t>(),
+                         st, c->kg_sk.as<uint32_t>(), c->v_blob_own.as<uint8_t>(),
                          c->v_off_own.as<uint64_t>() + j0, m, c->kg_out.as<uint8_t>(), c->digest);
     }
     if (hipGetLastError() != hipSuccess) rc = fail(c, HBX_E_DEVICE, "hbx_sk_decrypt: device error");

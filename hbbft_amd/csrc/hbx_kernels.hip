@@ -671,6 +671,54 @@ __global__ void __launch_bounds__(64) k_verify_sig_shares2_fe(uint32_t n, uint8_
 }
 template __global__ void k_verify_sig_shares2_fe<true>(uint32_t, uint8_t*, uint32_t*, uint32_t, uint32_t*);
 template __global__ void k_verify_sig_shares2_fe<false>(uint32_t, uint8_t*, uint32_t*, uint32_t, uint32_t*);
+
+// Ciphertext::verify on a lane pair (hbx_sk_decrypt in HBX_CT_CHECK_PAIR mode): e(U_j, H'_j) e(-[m] g1, W_j)
+// == 1 with H' = [m] H (k_prepare_ct), so the verdict is the reference's e(g1, W) == e(U, H).  Both G2
+// points differ per ciphertext, so each lane generates its own pair's lines (miller_gen2d): lane 0
+// (H'_j, U_j), lane 1 (W_j, -[m] g1).  No prepared line tables: the state per ciphertext is the
+// decode's points and the pair's global slot.  k_verify_sig_shares2_fe runs the final exponentiation
+// of the pending pairs (grid.y = 1, n = p) and writes HBX_SHARE_VALID / INVALID, which equal
+// HBX_CT_VALID / INVALID, so `st` is the call's status output.
+//   * gate: k_prepare_lines' rule on k_prepare_ct's decode statuses -- U_j and W_j must each be a
+//     subgroup point or the identity, else HBX_CT_UNDECODABLE and no pairing;
+//   * H' arrives Jacobian (Hj; G2pts[2j] holds only its identity flag): lane 0 makes it affine, one
+//     Fq2 inversion per ciphertext, and keeps it in G2pts[2j], where the loop's addition steps re-read it;
+//   * W's membership in G2 was decided by the decode, so lane 1's T = [|x|] W is not used.
+__global__ void __launch_bounds__(64) k_verify_ct2(const g1a* __restrict__ U, g2a* G2pts, const g2j* __restrict__ Hj,
+                                                   const int32_t* __restrict__ dec_st, uint32_t p,
+                                                   uint8_t* __restrict__ st, uint32_t* __restrict__ gslot,
+                                                   uint32_t retry) {
+  __shared__ uint32_t region[LDS2_DWORDS * 64];
+  const int lane = (int)(threadIdx.x & 63);
+  const bool l1 = (lane & 1) != 0;
+  const uint32_t i = blockIdx.x * 32 + (uint32_t)(lane >> 1);
+  if (i >= p) return;  // whole pairs
+  // retry: only the pairs k_verify_sig_shares2_fe<true> sent back (SHARE_FALLBACK), Miller again
+  if (retry && st[i] != SHARE_FALLBACK) return;  // pair-uniform
+  const int32_t su = dec_st[i], sw = dec_st[p + i];
+  const bool ok = (su == HBX_PT_OK || su == HBX_PT_INFINITY) && (sw == HBX_PT_OK || sw == HBX_PT_INFINITY);
+  if (ok) {  // pair-uniform
+    g2a* qp = G2pts + 2 * (size_t)i + (l1 ? 1 : 0);
+    g1a P;
+    if (l1) {
+      P.x = fq_from_const(G1_MGEN_X);
+      P.y = fq_neg(fq_from_const(G1_MGEN_Y));
+      P.inf = false;
+    } else {
+      P = U[i];
+      if (!qp->inf) *qp = g2_to_affine(Hj[i]);  // no lane exchange in here: lane 1 waits
+    }
+    const bool use = !(qp->inf || P.inf);  // a pairing with the identity contributes 1
+    lds_u32* reg = (lds_u32*)region;
+    const int pl = lane & ~1;
+    g2jd T;
+    const fq6d f = miller_gen2d(qp, fqd_from_fq(P.x), fqd_from_fq(P.y), use, l1, (lds2)(reg + lane), reg + pl, T);
+    // this lane's half of f_A f_B to the pair's global slot
+    uint32_t* gb = gslot + (size_t)blockIdx.x * (2 * LDS_FQ6D_PACKED * 64) + pl;
+    slot_put_fq6d(gb + (l1 ? 1 : 0), 64u, fq6d_reduce(f));
+  }
+  if (!l1) st[i] = ok ? SHARE_PENDING : (uint8_t)HBX_CT_UNDECODABLE;
+}
 #endif
 
 constexpr int COMBINE_THREADS = 256;

@@ -103,6 +103,8 @@ EXPORTS = (
     "hbx_merkle_build_ragged_d",
     "hbx_merkle_validate_ragged_d",
     "hbx_broadcast_decode_ragged_d",
+    "hbx_set_ct_check",
+    "hbx_get_ct_check_used",
 )
 
 DIGEST_SHA256 = 0
@@ -120,6 +122,13 @@ SHARE_UNKNOWN_SENDER = 5
 CT_INVALID = 0
 CT_VALID = 1
 CT_UNDECODABLE = 3
+
+# Ciphertext::verify of hbx_sk_decrypt (include/hbx.h HBX_CT_CHECK_*): the wide executor over prepared
+# line tables (default), or one lane pair per ciphertext
+CT_CHECK_WIDE = 0
+CT_CHECK_PAIR = 1
+# ciphertexts per pass of hbx_sk_decrypt in pair mode (hbbft_amd/csrc/hbx_api.hip SK_DECRYPT_PAIR_CHUNK)
+SK_DECRYPT_PAIR_CHUNK = 16384
 
 # kernel ids of hbx_kernel_time (include/hbx.h)
 KERNELS = {"prepare_ct": 0, "prepare_lines": 1, "ct_checks": 2, "verify_shares": 3, "combine": 4,
@@ -241,6 +250,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.hbx_merkle_build_ragged_d.argtypes = [P, P, u64, P, P, P, u32, u32, P, P, P]
         lib.hbx_merkle_validate_ragged_d.argtypes = [P, P, u64, P, P, P, P, P, P, P, u32, u32, P, P]
         lib.hbx_broadcast_decode_ragged_d.argtypes = [P, P, u64, P, P, P, P, P, P, u32, u32, u32, P, u64, P, P, P, P]
+    # pair-lane Ciphertext::verify of hbx_sk_decrypt: absent from a library built before it
+    if hasattr(lib, "hbx_set_ct_check"):
+        lib.hbx_set_ct_check.argtypes = [P, ctypes.c_int]
+        lib.hbx_get_ct_check_used.argtypes = [P]
     _lib = lib
     return lib
 
@@ -338,11 +351,24 @@ class Context:
         self._check(self.lib.hbx_debug_force_fallback(self.h, every))
 
     def fallback_lanes(self) -> int:
-        """hbx_get_fallback_lanes: lanes of the last one-lane launch the fallback check decided."""
+        """hbx_get_fallback_lanes: checks of the last launch with a fallback path (one-lane decryption
+        shares, two-lane coin, pair-lane ciphertexts of ``sk_decrypt``) that the fallback decided."""
         v = int(self.lib.hbx_get_fallback_lanes(self.h))
         if v < 0:
             self._check(v)
         return v
+
+    def set_ct_check(self, mode: int):
+        """hbx_set_ct_check: how ``sk_decrypt`` runs Ciphertext::verify -- CT_CHECK_WIDE (default, the
+        wide executor over prepared line tables) or CT_CHECK_PAIR (one lane pair per ciphertext, no
+        tables).  Same statuses and plaintexts; the epoch's prepares are not affected."""
+        if isinstance(mode, bool) or mode not in (CT_CHECK_WIDE, CT_CHECK_PAIR):
+            raise ValueError(f"set_ct_check: CT_CHECK_WIDE (0) or CT_CHECK_PAIR (1), not {mode!r}")
+        self._check(self.lib.hbx_set_ct_check(self.h, int(mode)))
+
+    def ct_check_used(self) -> int:
+        """hbx_get_ct_check_used: the mode the last ``sk_decrypt`` ran (-1 before any call)."""
+        return int(self.lib.hbx_get_ct_check_used(self.h))
 
     def set_batch_verify(self, seed: Optional[bytes]):
         """hbx_set_batch_verify: decide each proposer's column of shares by one random-linear-combination

@@ -15,6 +15,9 @@ Messages:  Part = (commit uint8[(t+1)(t+2)/2, 48], rows = n ciphertexts (u48, v,
 
 Plaintext framing goes through a codec object; ``RawCodec`` (the default) is the raw-scalar form of
 DESIGN.md 4.5.  A bincode codec can replace it without touching the engine.
+
+``ct_check`` chooses how the replay's ``sk_decrypt`` runs Ciphertext::verify (``hbx.CT_CHECK_WIDE`` /
+``hbx.CT_CHECK_PAIR``, set on the context before each such call); None leaves the context's mode alone.
 """
 from __future__ import annotations
 
@@ -77,8 +80,11 @@ class _PartState:
 
 class KeyGenReplay:
     def __init__(self, ctx: "hbx.Context", our_idx: Optional[int], sec_key: bytes, pub_keys: np.ndarray,
-                 threshold: int, codec=None):
+                 threshold: int, codec=None, ct_check: Optional[int] = None):
+        if ct_check is not None and ct_check not in (hbx.CT_CHECK_WIDE, hbx.CT_CHECK_PAIR):
+            raise ValueError(f"KeyGenReplay: ct_check None, CT_CHECK_WIDE (0) or CT_CHECK_PAIR (1), not {ct_check!r}")
         self.ctx = ctx
+        self.ct_check = ct_check
         self.our_idx = our_idx  # None: an observer
         self.sec_key = bytes(sec_key)
         self.pub_keys = np.ascontiguousarray(pub_keys, dtype=np.uint8)
@@ -130,6 +136,8 @@ class KeyGenReplay:
                     ack_jobs.append((k, sender, proposer, values[me]))
         if not part_jobs and not ack_jobs:
             return out, {}
+        if self.ct_check is not None:
+            self.ctx.set_ct_check(self.ct_check)
         plains, st = self.ctx.sk_decrypt(self.sec_key, [j[2] for j in part_jobs] + [j[3] for j in ack_jobs])
         acks = self._finish_parts(part_jobs, plains, st, out, ack_randomness or {})
         self._finish_acks(ack_jobs, plains[len(part_jobs):], st[len(part_jobs):], out)

@@ -115,7 +115,7 @@ const char* hbx_build_id(void);
  * number of launches since the last hbx_set_timing call. */
 #define HBX_K_PREPARE_CT 0      /* hash_g1_g2 + decode of U/W per proposer */
 #define HBX_K_PREPARE_LINES 1   /* prepared Miller lines of H_j, W_j (and coin H) */
-#define HBX_K_CT_CHECKS 2       /* Ciphertext::verify pairing checks (wide executor) */
+#define HBX_K_CT_CHECKS 2       /* Ciphertext::verify pairing checks (wide executor; hbx_sk_decrypt in pair mode: k_verify_ct2 + final exponentiation) */
 #define HBX_K_VERIFY_SHARES 3   /* decryption-share pairing checks */
 #define HBX_K_COMBINE 4         /* Lagrange combine + key derivation per proposer */
 #define HBX_K_VERIFY_SIG 5      /* coin signature-share checks */
@@ -152,8 +152,9 @@ int hbx_set_digest(hbx_ctx* ctx, int variant);
 int hbx_set_verify_lanes(hbx_ctx* ctx, int lanes);
 /* Lanes per check the last decryption-share launch used (1, 2, 3, 6 or 7; 0 before any launch). */
 int hbx_get_verify_lanes_used(const hbx_ctx* ctx);
-/* Tests only: in one-lane decryption-share checks and two-lane coin checks, treat the check of
- * every `every`-th sender (0 = none, the default) as if its compressed squarings had met a zero
+/* Tests only: in one-lane decryption-share checks, two-lane coin checks and pair-lane ciphertext
+ * checks (hbx_set_ct_check), treat the check of every `every`-th sender, or every `every`-th
+ * ciphertext of a chunk (0 = none, the default), as if its compressed squarings had met a zero
  * denominator, so the fallback path decides it (the single-kernel one-lane check; for the coin, the
  * pair's Miller loop again and a final exponentiation without compressed runs).  Results are
  * unchanged.  (Real inputs reach that path only through an element with a zero Fq2 coefficient at
@@ -161,9 +162,10 @@ int hbx_get_verify_lanes_used(const hbx_ctx* ctx);
  * can choose -- a ciphertext with r = 3(x^2 - 1), for which every honest share's check is 1 after
  * the easy part -- is decided by the first step without a fallback.) */
 int hbx_debug_force_fallback(hbx_ctx* ctx, uint32_t every);
-/* Checks of the last share-check launch (decryption-share or coin, whichever came last) that the
- * fallback path decided: 0 unless hbx_debug_force_fallback is on, and 0 when that launch used a lane
- * count without a fallback path (decryption shares at lanes 2/3/6/7, coin at one lane).  The two
+/* Checks of the last share-check launch (decryption-share, coin, or the pair-lane ciphertext checks
+ * of hbx_sk_decrypt, summed over that call's chunks -- whichever came last) that the fallback path
+ * decided: 0 unless hbx_debug_force_fallback is on, and 0 when that launch used a lane
+ * count without a fallback path (decryption shares at lanes 2/3/6/7, coin at one lane).  The three
  * kinds count separately; "last" is host call order, so the value is meaningful when the caller
  * reads it after the launch it asks about (waits for the context's streams).  Diagnostics: no
  * reference counterpart. */
@@ -407,9 +409,16 @@ int hbx_bivar_check_acks(hbx_ctx* ctx, const uint8_t* commit48, uint32_t p, uint
  *   (:444): Ciphertext::verify, then V xor hash_bytes(sk U, |V|), under the node's individual secret
  *   key sk32 (not its threshold share).  status[count] = HBX_CT_*; out_blob (at the v_off offsets)
  *   holds the plaintext where the status is HBX_CT_VALID and zeros elsewhere (the reference returns
- *   None there).  Ciphertext::verify runs through the prepared-ciphertext path in chunks; own-share
- *   mode stays as it was, but the epoch's prepared ciphertexts are void afterwards, as after
- *   hbx_set_digest (a share verification then returns HBX_E_NO_CIPHERTEXTS until the next prepare).
+ *   None there).  Ciphertext::verify runs through the prepared-ciphertext path in chunks, or, after
+ *   hbx_set_ct_check(HBX_CT_CHECK_PAIR), on one lane pair per ciphertext without prepared line tables
+ *   (larger chunks, about 2 KiB of device state per ciphertext instead of about 100 KiB; the same
+ *   status bytes and plaintexts).  In either mode own-share mode stays as it was, but the epoch's
+ *   prepared ciphertexts are void afterwards, as after hbx_set_digest (a share verification then
+ *   returns HBX_E_NO_CIPHERTEXTS until the next prepare).
+ * hbx_set_ct_check -- how hbx_sk_decrypt runs Ciphertext::verify: HBX_CT_CHECK_WIDE (default) or
+ *   HBX_CT_CHECK_PAIR; any other value is HBX_E_INVALID_ARG.  No reference counterpart; it governs
+ *   hbx_sk_decrypt only (the epoch's prepares keep the wide executor or the own-share fusion).
+ * hbx_get_ct_check_used -- the mode the last hbx_sk_decrypt ran; -1 before any call.
  * hbx_bivar_poly_rows -- BivarPoly::row(x) for x = 1..n (:293 `our_part.row(i + 1)`) of the dealer's
  *   polynomial coeff32[(t+1)(t+2)/2][32] in coeff_pos order: rows32[n][t + 1][32].
  * hbx_fr_poly_eval -- Poly::evaluate (:341 `row.evaluate(idx + 1)`) of p polynomials
@@ -431,6 +440,10 @@ int hbx_encrypt_to(hbx_ctx* ctx, const uint8_t* pk48, const uint8_t* msg_blob, c
                    uint32_t count, const uint8_t* r32, uint8_t* u48, uint8_t* v_blob, uint8_t* w96);
 int hbx_sk_decrypt(hbx_ctx* ctx, const uint8_t* sk32, const uint8_t* u48, const uint8_t* v_blob,
                    const uint64_t* v_off, const uint8_t* w96, uint32_t count, uint8_t* out_blob, uint8_t* status);
+#define HBX_CT_CHECK_WIDE 0
+#define HBX_CT_CHECK_PAIR 1
+int hbx_set_ct_check(hbx_ctx* ctx, int mode);
+int hbx_get_ct_check_used(const hbx_ctx* ctx);
 int hbx_bivar_poly_rows(hbx_ctx* ctx, const uint8_t* coeff32, uint32_t t, uint32_t n, uint8_t* rows32);
 int hbx_fr_poly_eval(hbx_ctx* ctx, const uint8_t* coeff32, uint32_t p, uint32_t t, uint32_t n, uint8_t* out32);
 int hbx_keygen_generate(hbx_ctx* ctx, const uint8_t* commit48, uint32_t p, uint32_t t, const uint8_t* complete,

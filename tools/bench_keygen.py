@@ -1,6 +1,6 @@
 """One node's SyncKeyGen era (reference src/sync_key_gen.rs) through the batch calls, stage by stage.
 
-    python tools/bench_keygen.py [--n 64] [--try-256] [--limit-s 240]
+    python tools/bench_keygen.py [--n 64] [--try-256] [--limit-s 240] [--ct-check wide|pair|both]
 
 Synthetic seeded data: N dealers' symmetric bivariate polynomials of degree t = (N - 1) / 3, their N
 Parts (this node's row of each, encrypted to its key) and the N^2 Acks addressed to this node (one
@@ -27,6 +27,12 @@ the script's own time limit (--limit-s, counted from the start of the script): i
 the measured N = 64 pass predicts it will not fit (the N^2 stages scale by 16), and once started the
 limit is checked before every input-building step and every stage; a pass that runs out reports the
 stages it finished and "stopped_before".  A stage already running is not interrupted.
+
+--ct-check chooses how hbx_sk_decrypt runs Ciphertext::verify (hbx_set_ct_check): `wide` (default, the
+wide executor over prepared line tables), `pair` (one lane pair per ciphertext) or `both`.  Every era
+carries a "ct_check" field.  With `both` the era runs once per mode at each size and the modes
+alternate (wide, pair at N = 64, then wide, pair at N = 256): "era" / "era_256" are the wide passes,
+"era_pair" / "era_256_pair" the pair passes, and the N = 256 prediction counts both passes.
 """
 from __future__ import annotations
 
@@ -51,11 +57,15 @@ def _scalars(rng, *shape):
     return a
 
 
+MODE_NAMES = {0: "wide", 1: "pair"}  # hbx.CT_CHECK_WIDE / hbx.CT_CHECK_PAIR
+
+
 class OutOfTime(Exception):
     pass
 
 
-def era(ctx, n: int, seed: int = 1, deadline: float = None):
+def era(ctx, n: int, seed: int = 1, deadline: float = None, ct_check: int = 0):
+    ctx.set_ct_check(ct_check)
     t = (n - 1) // 3
     M = (t + 1) * (t + 2) // 2
     me = n // 3
@@ -64,7 +74,7 @@ def era(ctx, n: int, seed: int = 1, deadline: float = None):
 
     def check(name):
         if deadline is not None and time.perf_counter() > deadline:
-            raise OutOfTime({"n": n, "stopped_before": name, "stage_ms": times})
+            raise OutOfTime({"n": n, "ct_check": MODE_NAMES[ct_check], "stopped_before": name, "stage_ms": times})
 
     def timed(name, fn, *args):
         check(name)
@@ -130,7 +140,8 @@ def era(ctx, n: int, seed: int = 1, deadline: float = None):
     assert (mine[0] == pk_shares[me]).all()
 
     verify_ms = sum(split[k][0] for k in ("prepare_ct", "prepare_lines", "ct_checks"))
-    return {"n": n, "t": t, "parts": n, "acks": n * n, "stage_ms": times,
+    assert ctx.ct_check_used() == ct_check
+    return {"n": n, "t": t, "parts": n, "acks": n * n, "ct_check": MODE_NAMES[ct_check], "stage_ms": times,
             "era_ms": round(sum(times.values()), 3),
             "ack_decrypt_kernels_ms": {"ciphertext_verify": round(verify_ms, 3),
                                        "prepare_ct": round(split["prepare_ct"][0], 3),
@@ -144,25 +155,38 @@ def main():
     ap.add_argument("--n", type=int, default=64)
     ap.add_argument("--try-256", action="store_true")
     ap.add_argument("--limit-s", type=float, default=240.0)
+    ap.add_argument("--ct-check", choices=("wide", "pair", "both"), default="wide")
     args = ap.parse_args()
     from hbbft_amd.hbx import Context, build_info
 
+    modes = {"wide": [0], "pair": [1], "both": [0, 1]}[args.ct_check]
+
+    def key(base, mode):  # with `both`, the pair pass goes beside the wide one
+        return base if mode == modes[0] else base + "_" + MODE_NAMES[mode]
+
     t0 = time.perf_counter()
     with Context(0) as ctx:
-        era(ctx, 4)  # warm-up: module load, first allocations
-        out = {"metric": "keygen_era", "lib": build_info(), "era": era(ctx, args.n)}
-        if args.try_256:
-            spent = time.perf_counter() - t0
-            # the whole N = 64 pass (inputs included) scaled by the N^2 stages' factor
-            predicted = spent * (256 / args.n) ** 2
-            if predicted <= args.limit_s:
-                try:
-                    out["era_256"] = era(ctx, 256, deadline=t0 + args.limit_s)
-                except OutOfTime as e:
-                    ctx.set_timing(False)
-                    out["era_256"] = e.args[0]
-            else:
-                out["era_256"] = {"skipped": f"predicted {predicted:.0f} s > limit {args.limit_s:.0f} s"}
+        try:
+            for mode in modes:
+                era(ctx, 4, ct_check=mode)  # warm-up: module load, first allocations
+            out = {"metric": "keygen_era", "lib": build_info()}
+            for mode in modes:
+                out[key("era", mode)] = era(ctx, args.n, ct_check=mode)
+            if args.try_256:
+                spent = time.perf_counter() - t0
+                # the whole N = 64 pass (inputs included, every mode) scaled by the N^2 stages' factor
+                predicted = spent * (256 / args.n) ** 2
+                for mode in modes:
+                    if predicted <= args.limit_s:
+                        try:
+                            out[key("era_256", mode)] = era(ctx, 256, deadline=t0 + args.limit_s, ct_check=mode)
+                        except OutOfTime as e:
+                            ctx.set_timing(False)
+                            out[key("era_256", mode)] = e.args[0]
+                    else:
+                        out[key("era_256", mode)] = {"skipped": f"predicted {predicted:.0f} s > limit {args.limit_s:.0f} s"}
+        finally:
+            ctx.set_ct_check(0)
     print(json.dumps(out))
 
 

@@ -529,3 +529,29 @@ int hc_sk_decrypt(const uint8_t* sk32, const uint8_t* u48, const uint8_t* v, uin
   return 0;
 }
 }
+extern "C" {
+// The pair-lane Ciphertext::verify (k_verify_ct2 + k_verify_sig_shares2_fe) on one thread:
+// e(U, H') e(-[m] g1, W) == 1 with H' = [m] hash_g1_g2(U, V), m = 3(x^2 - 1) (what k_prepare_ct's
+// group hash leaves in Hj), made affine, and both pairs' lines generated on the fly
+// (miller_loop_gen_d, the per-lane loop of the pair).  The decode is k_prepare_ct's: U in G1 and W
+// in G2, or the identity.  1 = verified, 0 = not, -1 = U or W undecodable.
+int hc_ct_check_gen(const uint8_t* u48, const uint8_t* v, uint64_t len, const uint8_t* w96, int digest) {
+  g1a U;
+  g2a W;
+  int32_t su = g1_decompress_d(u48, U);
+  if (su == HBX_PT_OK && !g1_is_torsion_free_d(U)) su = HBX_PT_NOT_IN_SUBGROUP;
+  int32_t sw = g2_decompress(w96, W);
+  if (sw == HBX_PT_OK && !g2_is_torsion_free(W)) sw = HBX_PT_NOT_IN_SUBGROUP;
+  if ((su != HBX_PT_OK && su != HBX_PT_INFINITY) || (sw != HBX_PT_OK && sw != HBX_PT_INFINITY)) return -1;
+  const g2a Hp = g2_to_affine(g2_mul_bits(hash_g1_g2(u48, v, len, digest), HEFF_M, 256));
+  fq12d f = fq12d_one();
+  g2jd T;
+  if (!U.inf && !Hp.inf)  // a pairing with the identity contributes 1
+    f = miller_loop_gen_d(fq2d_from_fq2(Hp.x), fq2d_from_fq2(Hp.y), fqd_from_fq(U.x), fqd_from_fq(U.y), T);
+  if (!W.inf)
+    f = fq12d_mul(f, miller_loop_gen_d(fq2d_from_fq2(W.x), fq2d_from_fq2(W.y), fqd_from_fq(fq_from_const(G1_MGEN_X)),
+                                       fqd_from_fq(fq_neg(fq_from_const(G1_MGEN_Y))), T));
+  static uint32_t slot[LDS_FQ12D_DWORDS];
+  return fq12d_is_one(final_exponentiation_d(f, slot)) ? 1 : 0;
+}
+}
