@@ -104,9 +104,10 @@ struct hbx_ctx {
   // u32 counters of the checks the fallback path decided: one for the one-lane decryption-share
   // checks, one for the two-lane coin checks, one for the pair-lane ciphertext checks of
   // hbx_sk_decrypt, summed over the call's chunks (launches of different kinds on different streams
-  // must not mix their counts); fb_last names the counter of the last launch of any kind, or none
+  // must not mix their counts), one for the pair-lane signature checks of hbx_verify_sigs_keyed, summed
+  // likewise; fb_last names the counter of the last launch of any kind, or none
   // when that launch used a lane count without a fallback path
-  dbuf fb_lanes, fb_coin, fb_ct;
+  dbuf fb_lanes, fb_coin, fb_ct, fb_sigs;
   dbuf* fb_last = nullptr;
   dbuf hs[6];                   // staging of the host-pointer broadcast calls
   // combine state
@@ -129,6 +130,9 @@ struct hbx_ctx {
       coin_valid, coin_comb, coin_comb_st, coin_mpk_comp, coin_mpk, coin_mpk_st, coin_ok, coin_par, coin_out96;
   // PublicKey::verify batches (hbx_verify_sigs)
   dbuf vs_pk, vs_blob, vs_off, vs_H, vs_lines, vs_lines_d, vs_scratch, vs_sig96, vs_sig, vs_sig_st, vs_status;
+  // the keyed form (hbx_verify_sigs_keyed / hbx_sign_msgs): the key table's bytes, points and HBX_PT_*,
+  // the items' key indices, the pairs' global slots of one pass, the signing key
+  dbuf vk_pk48, vk_pk, vk_pkst, vk_idx, vk_gslot, vk_sk;
   dbuf coin_lines_d;  // the nonces' lines in the coin check's digit form
   bool coin_lines_ready = false;  // coin_lines_d computed for the prepared nonces (one-lane checks only)
   uint8_t coin_mpk48[48] = {0};   // the master key coin_mpk was decoded from
@@ -635,7 +639,7 @@ int hbx_ctx_destroy(hbx_ctx* c) {
                   &c->coin_comb_st, &c->coin_mpk_comp, &c->coin_mpk, &c->coin_mpk_st, &c->coin_ok, &c->coin_par,
                   &c->coin_out96, &c->dec_st, &c->own_sk, &c->own_S, &c->own_part, &c->lines_d,
                   &c->vs_pk, &c->vs_lines_d, &c->coin_lines_d, &c->vs_blob, &c->vs_off, &c->vs_H, &c->vs_lines, &c->vs_scratch, &c->vs_sig96,
-                  &c->vs_sig, &c->vs_sig_st, &c->vs_status, &c->fe1slot, &c->fb_lanes, &c->fb_coin, &c->fb_ct, &c->hs[0], &c->hs[1], &c->hs[2], &c->hs[3], &c->hs[4], &c->hs[5], &c->coin_use, &c->bv_commit48, &c->bv_C, &c->bv_cst, &c->bv_rows,
+                  &c->vs_sig, &c->vs_sig_st, &c->vs_status, &c->fe1slot, &c->fb_lanes, &c->fb_coin, &c->fb_ct, &c->fb_sigs, &c->vk_pk48, &c->vk_pk, &c->vk_pkst, &c->vk_idx, &c->vk_gslot, &c->vk_sk, &c->hs[0], &c->hs[1], &c->hs[2], &c->hs[3], &c->hs[4], &c->hs[5], &c->coin_use, &c->bv_commit48, &c->bv_C, &c->bv_cst, &c->bv_rows,
                   &c->bv_rows48, &c->bv_pst, &c->bv_ackp, &c->bv_acky, &c->bv_vals, &c->bv_out,
                   &c->kg_sk, &c->kg_out, &c->kg_st, &c->b_seed, &c->b_AJ, &c->b_T, &c->b_C, &c->b_Asum, &c->b_A, &c->b_B,
                   &c->b_cls0, &c->b_cand, &c->b_pass, &c->b_zero, &c->b_cls, &c->b_ctok, &c->b_stats, &c->rg_dev};
@@ -2100,6 +2104,137 @@ int hbx_verify_sigs(hbx_ctx* c, const uint8_t* pk48, const uint8_t* msg_blob, co
   }
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(status, c->vs_status.p, count, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  return HBX_OK;
+}
+
+namespace {
+// Items per pass of hbx_verify_sigs_keyed and hbx_sign_msgs (hbbft_amd/hbx.py VERIFY_SIGS_CHUNK is the
+// same number).  The state is about 2 KiB per item (H' and sigma decoded, the pair's 1.25 KiB slot
+// for the halves of f, the compressed signature): 16,384 items are about 30 MB, 512 pair-check waves
+// and 4,096 hash waves, as in hbx_sk_decrypt's pair mode.
+constexpr uint32_t VERIFY_SIGS_CHUNK = 16384;
+
+// shared argument check of the two message calls; the total blob length in *total
+int msgs_check(hbx_ctx* c, const char* fn, const uint8_t* msg_blob, const uint64_t* msg_off, uint32_t count,
+               uint64_t* total) {
+  if (!msg_off || count == 0) return fail(c, HBX_E_INVALID_ARG, "%s: bad args", fn);
+  for (uint32_t i = 0; i < count; i++)
+    if (msg_off[i + 1] < msg_off[i]) return fail(c, HBX_E_INVALID_ARG, "%s: msg_off not monotone", fn);
+  *total = msg_off[count] - msg_off[0];
+  if (*total && !msg_blob) return fail(c, HBX_E_INVALID_ARG, "%s: null blob", fn);
+  return HBX_OK;
+}
+}  // namespace
+
+int hbx_verify_sigs_keyed(hbx_ctx* c, const uint8_t* pk48, uint32_t nkeys, const uint32_t* key_idx,
+                          const uint8_t* msg_blob, const uint64_t* msg_off, const uint8_t* sig96, uint32_t count,
+                          uint8_t* status, int32_t* key_status) {
+  if (!c || !pk48 || nkeys == 0 || !key_idx || !sig96 || !status)
+    return fail(c, HBX_E_INVALID_ARG, "hbx_verify_sigs_keyed: bad args");
+  uint64_t total = 0;
+  if (int rc = msgs_check(c, "hbx_verify_sigs_keyed", msg_blob, msg_off, count, &total)) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = pick(c, c->stream);
+  stream_scope ss_{c, s};
+  // every buffer is sized here, before the first pass: the per-item state for one chunk only
+  const size_t cap = std::min(VERIFY_SIGS_CHUNK, count);
+  const uint64_t base = msg_off[0], end = msg_off[count];
+  if (!c->vk_pk48.ensure((size_t)nkeys * 48) || !c->vk_pk.ensure((size_t)nkeys * sizeof(g1a)) ||
+      !c->vk_pkst.ensure((size_t)nkeys * 4) || !c->vk_idx.ensure((size_t)count * 4) ||
+      !c->vs_blob.ensure(end ? end : 16) || !c->vs_off.ensure((size_t)(count + 1) * 8) ||
+      !c->vs_sig96.ensure((size_t)count * 96) || !c->vs_status.ensure(count) || !c->vs_H.ensure(cap * sizeof(g2a)) ||
+      !c->vs_sig.ensure(cap * sizeof(g2a)) || !c->vs_sig_st.ensure(cap * 4) ||
+      !c->vk_gslot.ensure((cap + 31) / 32 * 64 * 2 * LDS_FQ6D_PACKED * 4) || !c->fb_sigs.ensure(4))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_verify_sigs_keyed: out of device memory");
+  HIPCHK(c, hipMemcpyAsync(c->vk_pk48.p, pk48, (size_t)nkeys * 48, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->vk_idx.p, key_idx, (size_t)count * 4, hipMemcpyHostToDevice, s));
+  if (total)
+    HIPCHK(c, hipMemcpyAsync(c->vs_blob.as<uint8_t>() + base, msg_blob + base, total, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->vs_off.p, msg_off, (size_t)(count + 1) * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->vs_sig96.p, sig96, (size_t)count * 96, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemsetAsync(c->fb_sigs.p, 0, 4, s));
+  c->fb_last = &c->fb_sigs;
+  // the key table once, one lane per key: decode = into_affine (curve + G1 membership), identity allowed
+  hipLaunchKernelGGL(k_decompress_shares, dim3((nkeys + 255) / 256), dim3(256), 0, s, c->vk_pk48.as<uint8_t>(),
+                     (size_t)nkeys, c->vk_pk.as<g1a>(), c->vk_pkst.as<int32_t>(), 1u, UINT32_MAX, nullptr);
+  HIPCHK(c, hipGetLastError());
+  if (key_status) HIPCHK(c, hipMemcpyAsync(key_status, c->vk_pkst.p, (size_t)nkeys * 4, hipMemcpyDeviceToHost, s));
+  for (uint32_t j0 = 0; j0 < count; j0 += VERIFY_SIGS_CHUNK) {
+    const uint32_t m = std::min(VERIFY_SIGS_CHUNK, count - j0);
+    uint8_t* st = c->vs_status.as<uint8_t>() + j0;
+    {
+      // H'_i = [m] hash_g2(msg_i), affine, against -[m] g1 (the coin checks' form)
+      timed t_(c, HBX_K_HASH_NONCES, s);
+      hipLaunchKernelGGL(k_hash_nonces, dim3((unsigned)(((size_t)m * HASH_K + 63) / 64)), dim3(64), 0, s,
+                         c->vs_blob.as<uint8_t>(), c->vs_off.as<uint64_t>() + j0, m, c->vs_H.as<g2a>(), c->digest, 0);
+    }
+    HIPCHK(c, hipGetLastError());
+    {
+      // curve membership only: the checks take G2 membership from their Miller loop's [|x|] sigma
+      timed t_(c, HBX_K_DECODE_SIGS, s);
+      hipLaunchKernelGGL(k_decompress_g2, dim3((m + 63) / 64), dim3(64), 0, s, c->vs_sig96.as<uint8_t>() + (size_t)j0 * 96,
+                         (size_t)m, c->vs_sig.as<g2a>(), c->vs_sig_st.as<int32_t>(), 0u);
+    }
+    HIPCHK(c, hipGetLastError());
+    {
+      timed t_(c, HBX_K_VERIFY_SIG, s);
+      const dim3 grid((m + 31) / 32);
+      // Miller loops; the final exponentiation with compressed runs; then the pairs it sent back
+      // (SHARE_FALLBACK) once more with Granger-Scott squarings only (hbx_sk_decrypt's pair mode)
+      for (uint32_t retry = 0; retry < 2; retry++) {
+        hipLaunchKernelGGL(k_verify_sigs2, grid, dim3(64), 0, s, c->vs_H.as<g2a>(), c->vk_pk.as<g1a>(),
+                           c->vk_pkst.as<int32_t>(), nkeys, c->vk_idx.as<uint32_t>() + j0, c->vs_sig.as<g2a>(),
+                           c->vs_sig_st.as<int32_t>(), m, st, c->vk_gslot.as<uint32_t>(), retry);
+        if (retry == 0)
+          hipLaunchKernelGGL(k_verify_sig_shares2_fe<true>, grid, dim3(64), 0, s, m, st, c->vk_gslot.as<uint32_t>(),
+                             c->force_fallback, c->fb_sigs.as<uint32_t>());
+        else
+          hipLaunchKernelGGL(k_verify_sig_shares2_fe<false>, grid, dim3(64), 0, s, m, st, c->vk_gslot.as<uint32_t>(), 0u,
+                             c->fb_sigs.as<uint32_t>());
+      }
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(status + j0, st, m, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(c, hipStreamSynchronize(s));
+  return HBX_OK;
+}
+
+int hbx_sign_msgs(hbx_ctx* c, const uint8_t* sk32, const uint8_t* msg_blob, const uint64_t* msg_off, uint32_t count,
+                  uint8_t* sig96) {
+  if (!c || !sk32 || !sig96) return fail(c, HBX_E_INVALID_ARG, "hbx_sign_msgs: bad args");
+  uint64_t total = 0;
+  if (int rc = msgs_check(c, "hbx_sign_msgs", msg_blob, msg_off, count, &total)) return rc;
+  static const uint8_t zero32[32] = {0};
+  if (!scalars_canonical(sk32, 1) || memcmp(sk32, zero32, 32) == 0)
+    return fail(c, HBX_E_INVALID_ARG, "hbx_sign_msgs: secret key not in [1, r)");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = pick(c, c->stream);
+  stream_scope ss_{c, s};
+  const size_t cap = std::min(VERIFY_SIGS_CHUNK, count);
+  const uint64_t base = msg_off[0], end = msg_off[count];
+  if (!c->vk_sk.ensure(32) || !c->vs_blob.ensure(end ? end : 16) || !c->vs_off.ensure((size_t)(count + 1) * 8) ||
+      !c->vs_sig96.ensure((size_t)count * 96) || !c->vs_H.ensure(cap * sizeof(g2a)))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_sign_msgs: out of device memory");
+  HIPCHK(c, hipMemcpyAsync(c->vk_sk.p, sk32, 32, hipMemcpyHostToDevice, s));
+  if (total)
+    HIPCHK(c, hipMemcpyAsync(c->vs_blob.as<uint8_t>() + base, msg_blob + base, total, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->vs_off.p, msg_off, (size_t)(count + 1) * 8, hipMemcpyHostToDevice, s));
+  for (uint32_t j0 = 0; j0 < count; j0 += VERIFY_SIGS_CHUNK) {
+    const uint32_t m = std::min(VERIFY_SIGS_CHUNK, count - j0);
+    {
+      timed t_(c, HBX_K_HASH_NONCES, s);
+      hipLaunchKernelGGL(k_hash_nonces, dim3((unsigned)(((size_t)m * HASH_K + 63) / 64)), dim3(64), 0, s,
+                         c->vs_blob.as<uint8_t>(), c->vs_off.as<uint64_t>() + j0, m, c->vs_H.as<g2a>(), c->digest, 1);
+    }
+    HIPCHK(c, hipGetLastError());
+    // SecretKey::sign: sk * H_i, one key (n = 1), one message per grid row
+    hipLaunchKernelGGL(k_sign, dim3(1, m), dim3(64), 0, s, c->vk_sk.as<uint8_t>(), 1u, c->vs_H.as<g2a>(),
+                       c->vs_sig96.as<uint8_t>() + (size_t)j0 * 96);
+    HIPCHK(c, hipGetLastError());
+  }
+  HIPCHK(c, hipMemcpyAsync(sig96, c->vs_sig96.p, (size_t)count * 96, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   return HBX_OK;
 }

@@ -719,6 +719,71 @@ __global__ void __launch_bounds__(64) k_verify_ct2(const g1a* __restrict__ U, g2
   }
   if (!l1) st[i] = ok ? SHARE_PENDING : (uint8_t)HBX_CT_UNDECODABLE;
 }
+
+// PublicKey::verify on a lane pair over a key table (hbx_verify_sigs_keyed; Dynamic HoneyBadger's
+// SignedKeyGenMsg checks, dynamic_honey_badger.rs:254-272 and :395-410): e(pk_k, H'_i) e(-[m] g1, sigma_i)
+// == 1 with k = key_idx[i] and H'_i = [m] hash_g2(msg_i) (k_hash_nonces with full = 0), the verdict of
+// e(pk_k, H_i) == e(g1, sigma_i).  k_verify_ct2's schedule: lane 0 (H'_i, pk_k), lane 1 (sigma_i,
+// -[m] g1), each lane its own lines (miller_gen2d), the halves of f to the pair's global slot, and
+// k_verify_sig_shares2_fe for the pending pairs (grid.y = 1, n = count).
+//   * status order: key_idx[i] >= nkeys is HBX_SHARE_UNKNOWN_SENDER (nothing else is read); a key
+//     that is neither a G1 point nor the identity, or a sigma that does not decode, is
+//     HBX_SHARE_UNDECODABLE; all of it pair-uniform, the pair then skips its loops;
+//   * sigma's membership in G2 comes from lane 1's T = [|x|] sigma, as in k_verify_sig_shares2 (the
+//     decode ran with subgroup = 0); sigma is re-read for the compare, not held across the loop;
+//   * H' arrives affine from k_hash_nonces, identity flag included: nothing to convert;
+//   * an identity on either side of a pairing makes that pairing 1 (miller_gen2d `use`), which gives
+//     k_verify_sigs' identity rules: both identities valid, exactly one invalid.
+__global__ void __launch_bounds__(64) k_verify_sigs2(const g2a* __restrict__ H, const g1a* __restrict__ pk,
+                                                     const int32_t* __restrict__ pk_st, uint32_t nkeys,
+                                                     const uint32_t* __restrict__ key_idx, const g2a* __restrict__ sig,
+                                                     const int32_t* __restrict__ sig_st, uint32_t count,
+                                                     uint8_t* __restrict__ st, uint32_t* __restrict__ gslot,
+                                                     uint32_t retry) {
+  __shared__ uint32_t region[LDS2_DWORDS * 64];
+  const int lane = (int)(threadIdx.x & 63);
+  const bool l1 = (lane & 1) != 0;
+  const uint32_t i = blockIdx.x * 32 + (uint32_t)(lane >> 1);
+  if (i >= count) return;  // whole pairs
+  // retry: only the pairs k_verify_sig_shares2_fe<true> sent back (SHARE_FALLBACK), Miller again
+  if (retry && st[i] != SHARE_FALLBACK) return;  // pair-uniform
+  const uint32_t k = key_idx[i];
+  uint8_t res = HBX_SHARE_VALID;
+  if (k >= nkeys) {
+    res = HBX_SHARE_UNKNOWN_SENDER;
+  } else {
+    const int32_t sk = pk_st[k], ss = sig_st[i];
+    if (!((sk == HBX_PT_OK || sk == HBX_PT_INFINITY) && (ss == HBX_PT_OK || ss == HBX_PT_INFINITY)))
+      res = HBX_SHARE_UNDECODABLE;
+  }
+  bool tf = true;
+  if (res == HBX_SHARE_VALID) {  // pair-uniform
+    const g2a* qp = l1 ? sig + i : H + i;
+    g1a P;
+    if (l1) {
+      P.x = fq_from_const(G1_MGEN_X);
+      P.y = fq_neg(fq_from_const(G1_MGEN_Y));
+      P.inf = false;
+    } else {
+      P = pk[k];
+    }
+    const bool use = !(qp->inf || P.inf);  // a pairing with the identity contributes 1
+    lds_u32* reg = (lds_u32*)region;
+    const int pl = lane & ~1;
+    g2jd T;
+    const fq6d f = miller_gen2d(qp, fqd_from_fq(P.x), fqd_from_fq(P.y), use, l1, (lds2)(reg + lane), reg + pl, T);
+    // this lane's half of f_A f_B to the pair's global slot
+    uint32_t* gb = gslot + (size_t)blockIdx.x * (2 * LDS_FQ6D_PACKED * 64) + pl;
+    slot_put_fq6d(gb + (l1 ? 1 : 0), 64u, fq6d_reduce(f));
+    // sigma in G2 from lane 1's T = [|x|] sigma; lane 0's T is H''s, a G2 point by construction
+    tf = !l1 || g2_torsion_free_from_T(T, *qp);
+  }
+  // lane 1's membership bit to lane 0, exchanged on every lane before the bits are combined
+  // (k_verify_sig_shares2: inside `tf && ...` lane 1 would skip the exchange)
+  const int tf_other = __shfl_xor((int)tf, 1);
+  const bool tf_pair = tf && tf_other != 0;
+  if (!l1) st[i] = res != HBX_SHARE_VALID ? res : tf_pair ? SHARE_PENDING : (uint8_t)HBX_SHARE_UNDECODABLE;
+}
 #endif
 
 constexpr int COMBINE_THREADS = 256;

@@ -105,6 +105,8 @@ EXPORTS = (
     "hbx_broadcast_decode_ragged_d",
     "hbx_set_ct_check",
     "hbx_get_ct_check_used",
+    "hbx_verify_sigs_keyed",
+    "hbx_sign_msgs",
 )
 
 DIGEST_SHA256 = 0
@@ -129,6 +131,10 @@ CT_CHECK_WIDE = 0
 CT_CHECK_PAIR = 1
 # ciphertexts per pass of hbx_sk_decrypt in pair mode (hbbft_amd/csrc/hbx_api.hip SK_DECRYPT_PAIR_CHUNK)
 SK_DECRYPT_PAIR_CHUNK = 16384
+# items per pass of hbx_verify_sigs_keyed / hbx_sign_msgs (hbbft_amd/csrc/hbx_api.hip VERIFY_SIGS_CHUNK)
+VERIFY_SIGS_CHUNK = 16384
+# key_idx value of an item without a key (the reference's pk_opt is None): HBX_SHARE_UNKNOWN_SENDER
+NO_KEY = 0xFFFFFFFF
 
 # kernel ids of hbx_kernel_time (include/hbx.h)
 KERNELS = {"prepare_ct": 0, "prepare_lines": 1, "ct_checks": 2, "verify_shares": 3, "combine": 4,
@@ -254,6 +260,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     if hasattr(lib, "hbx_set_ct_check"):
         lib.hbx_set_ct_check.argtypes = [P, ctypes.c_int]
         lib.hbx_get_ct_check_used.argtypes = [P]
+    # PublicKey::verify over a key table and SecretKey::sign: absent from a library built before them
+    # (tools/bench_keygen.py --lib times such a build through hbx_verify_sigs)
+    if hasattr(lib, "hbx_verify_sigs_keyed"):
+        lib.hbx_verify_sigs_keyed.argtypes = [P, u8p, u32, ctypes.POINTER(ctypes.c_uint32), u8p, u64p, u8p, u32, u8p,
+                                              i32p]
+        lib.hbx_sign_msgs.argtypes = [P, u8p, u8p, u64p, u32, u8p]
     _lib = lib
     return lib
 
@@ -352,7 +364,8 @@ class Context:
 
     def fallback_lanes(self) -> int:
         """hbx_get_fallback_lanes: checks of the last launch with a fallback path (one-lane decryption
-        shares, two-lane coin, pair-lane ciphertexts of ``sk_decrypt``) that the fallback decided."""
+        shares, two-lane coin, pair-lane ciphertexts of ``sk_decrypt``, pair-lane signatures of
+        ``verify_sigs_keyed``) that the fallback decided."""
         v = int(self.lib.hbx_get_fallback_lanes(self.h))
         if v < 0:
             self._check(v)
@@ -636,6 +649,52 @@ class Context:
         self._check(self.lib.hbx_verify_sigs(self.h, _u8(pk48), _u8(blob),
                                              off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), _u8(sig96), count,
                                              _u8(out)))
+        return out
+
+    @staticmethod
+    def _msg_blob(msgs):
+        off = np.zeros(len(msgs) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(m) for m in msgs])
+        return np.frombuffer(b"".join(msgs) or b"\0", dtype=np.uint8).copy(), off
+
+    def verify_sigs_keyed(self, pk48: np.ndarray, key_idx: np.ndarray, msgs, sig96: np.ndarray):
+        """PublicKey::verify(sig_i, msg_i) under pk48[key_idx[i]] (hbx_verify_sigs_keyed): the signed
+        key-generation messages of an era, or a batch of votes.  pk48 uint8[nkeys, 48], key_idx
+        uint32[count] (NO_KEY, or any index >= nkeys: SHARE_UNKNOWN_SENDER), msgs = list of bytes,
+        sig96 uint8[count, 96] -> (HBX_SHARE_* uint8[count], HBX_PT_* int32[nkeys])."""
+        pk48 = np.ascontiguousarray(pk48, dtype=np.uint8)
+        sig96 = np.ascontiguousarray(sig96, dtype=np.uint8)
+        count = len(msgs)
+        if pk48.ndim != 2 or pk48.shape[1] != 48 or pk48.shape[0] == 0:
+            raise ValueError("verify_sigs_keyed: pk48 must be uint8[nkeys, 48] with nkeys > 0")
+        if not isinstance(key_idx, np.ndarray) or key_idx.dtype != np.uint32 or key_idx.shape != (count,):
+            raise ValueError(f"verify_sigs_keyed: key_idx must be a uint32[{count}] array")
+        if count == 0 or sig96.shape != (count, 96):
+            raise ValueError("verify_sigs_keyed: key_idx, msgs and sig96 must have the same non-zero count")
+        key_idx = np.ascontiguousarray(key_idx)
+        nkeys = pk48.shape[0]
+        blob, off = self._msg_blob(msgs)
+        out = np.zeros(count, dtype=np.uint8)
+        kst = np.zeros(nkeys, dtype=np.int32)
+        self._check(self.lib.hbx_verify_sigs_keyed(self.h, _u8(pk48), nkeys,
+                                                   key_idx.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), _u8(blob),
+                                                   off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), _u8(sig96), count,
+                                                   _u8(out), kst.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        return out, kst
+
+    def sign_msgs(self, sk32: bytes, msgs) -> np.ndarray:
+        """SecretKey::sign of every message under sk32 (32 bytes, big-endian, in [1, r)) ->
+        uint8[count, 96] (hbx_sign_msgs).  Leaves the coin's prepared nonces alone."""
+        sk = np.frombuffer(bytes(sk32), dtype=np.uint8).copy()
+        count = len(msgs)
+        if sk.size != 32:
+            raise ValueError("sign_msgs: sk32 must be 32 bytes")
+        if count == 0:
+            raise ValueError("sign_msgs: no messages")
+        blob, off = self._msg_blob(msgs)
+        out = np.zeros((count, 96), dtype=np.uint8)
+        self._check(self.lib.hbx_sign_msgs(self.h, _u8(sk), _u8(blob), off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                           count, _u8(out)))
         return out
 
     def bivar_rows(self, commits: np.ndarray, t: int, x: int):

@@ -162,10 +162,11 @@ int hbx_get_verify_lanes_used(const hbx_ctx* ctx);
  * can choose -- a ciphertext with r = 3(x^2 - 1), for which every honest share's check is 1 after
  * the easy part -- is decided by the first step without a fallback.) */
 int hbx_debug_force_fallback(hbx_ctx* ctx, uint32_t every);
-/* Checks of the last share-check launch (decryption-share, coin, or the pair-lane ciphertext checks
- * of hbx_sk_decrypt, summed over that call's chunks -- whichever came last) that the fallback path
+/* Checks of the last share-check launch (decryption-share, coin, the pair-lane ciphertext checks
+ * of hbx_sk_decrypt or the pair-lane signature checks of hbx_verify_sigs_keyed, the latter two
+ * summed over that call's chunks -- whichever came last) that the fallback path
  * decided: 0 unless hbx_debug_force_fallback is on, and 0 when that launch used a lane
- * count without a fallback path (decryption shares at lanes 2/3/6/7, coin at one lane).  The three
+ * count without a fallback path (decryption shares at lanes 2/3/6/7, coin at one lane).  The four
  * kinds count separately; "last" is host call order, so the value is meaningful when the caller
  * reads it after the launch it asks about (waits for the context's streams).  Diagnostics: no
  * reference counterpart. */
@@ -376,6 +377,38 @@ int hbx_get_coin_lanes_used(const hbx_ctx* ctx);
  * ------------------------------------------------------------------------------------------- */
 int hbx_verify_sigs(hbx_ctx* ctx, const uint8_t* pk48, const uint8_t* msg_blob, const uint64_t* msg_off,
                     const uint8_t* sig96, uint32_t count, uint8_t* status);
+/* hbx_verify_sigs_keyed -- the same check at the scale of a key-generation era, over a key table:
+ * item i is verified under pk48[key_idx[i]].  Dynamic HoneyBadger checks every committed
+ * SignedKeyGenMsg this way before handle_part / handle_ack sees it
+ * (src/dynamic_honey_badger/dynamic_honey_badger.rs:254-272 process_output, and :395-410
+ * verify_signature on arrival); a batch of signed votes (votes.rs:151-156) is a small call of the
+ * same kind.  An era at N validators is N Parts + N^2 Acks under N distinct keys.
+ *   pk48[nkeys][48]: decoded once per call (curve + G1 membership, the identity allowed);
+ *   key_status (optional, nkeys entries) receives HBX_PT_* per key.
+ *   key_idx[count], msg_off[count + 1] into msg_blob, sig96[count][96].
+ *   status[i], decided in this order:
+ *     HBX_SHARE_UNKNOWN_SENDER  key_idx[i] >= nkeys (0xFFFFFFFF is the "no key" value: the
+ *                               reference's pk_opt is None); nothing else of the item is examined;
+ *     HBX_SHARE_UNDECODABLE     the key's status is neither HBX_PT_OK nor HBX_PT_INFINITY, or the
+ *                               signature bytes are not a point of G2;
+ *     HBX_SHARE_VALID / HBX_SHARE_INVALID otherwise, with hbx_verify_sigs' identity rules (identity
+ *                               key and identity signature: valid; exactly one identity: invalid).
+ *   With nkeys == count and key_idx[i] = i the status bytes equal hbx_verify_sigs'.
+ *   The items run in passes of 16,384 on lane pairs, without prepared line tables (about 2 KiB of
+ *   device state per item of a pass).  hash_g2 uses the context's digest (hbx_set_digest).  The call
+ *   blocks, and leaves the prepared ciphertexts and the coin state as they were.
+ *   count == 0, nkeys == 0, a NULL required pointer or non-monotone offsets: HBX_E_INVALID_ARG before
+ *   anything is launched.  hbx_debug_force_fallback applies per pass; hbx_get_fallback_lanes counts
+ *   these checks as a kind of their own, summed over the call's passes.
+ * hbx_sign_msgs -- threshold_crypto SecretKey::sign, which send_transaction
+ * (dynamic_honey_badger.rs:363) runs on every Part and Ack a node sends and votes.rs:151-156 on every
+ * vote: sig96[i] = compress(sk * hash_g2(msg_i)) under the context's digest.  sk32 is canonical
+ * big-endian in [1, r) (HBX_E_INVALID_ARG otherwise).  Passes as above; no coin state is touched. */
+int hbx_verify_sigs_keyed(hbx_ctx* ctx, const uint8_t* pk48, uint32_t nkeys, const uint32_t* key_idx,
+                          const uint8_t* msg_blob, const uint64_t* msg_off, const uint8_t* sig96,
+                          uint32_t count, uint8_t* status, int32_t* key_status /* optional, nkeys */);
+int hbx_sign_msgs(hbx_ctx* ctx, const uint8_t* sk32, const uint8_t* msg_blob, const uint64_t* msg_off,
+                  uint32_t count, uint8_t* sig96);
 /* SyncKeyGen (src/sync_key_gen.rs) commitment checks over p Parts' BivarCommitments of degree t:
  *   commit48[p][(t+1)(t+2)/2][48], compressed, in threshold_crypto's coefficient order
  *   coeff_pos(i, j) = j (j + 1)/2 + i for i <= j (the symmetric matrix stored once).

@@ -1,6 +1,7 @@
 """One node's SyncKeyGen era (reference src/sync_key_gen.rs) through the batch calls, stage by stage.
 
     python tools/bench_keygen.py [--n 64] [--try-256] [--limit-s 240] [--ct-check wide|pair|both]
+                                 [--sig-path keyed|legacy|both] [--sig-msg-len 64] [--sigs-only]
 
 Synthetic seeded data: N dealers' symmetric bivariate polynomials of degree t = (N - 1) / 3, their N
 Parts (this node's row of each, encrypted to its key) and the N^2 Acks addressed to this node (one
@@ -33,6 +34,18 @@ wide executor over prepared line tables), `pair` (one lane pair per ciphertext) 
 carries a "ct_check" field.  With `both` the era runs once per mode at each size and the modes
 alternate (wide, pair at N = 64, then wide, pair at N = 256): "era" / "era_256" are the wide passes,
 "era_pair" / "era_256_pair" the pair passes, and the N = 256 prediction counts both passes.
+
+--sig-path adds the signature layer Dynamic HoneyBadger wraps around those messages
+(dynamic_honey_badger.rs:254-272, :363), in "sigs" / "sigs_256":
+  kg_sign         SecretKey::sign of this node's N + 1 messages (hbx_sign_msgs)
+  kg_sig_verify   PublicKey::verify of the era's N Parts + N^2 Acks over the table of N keys
+`keyed` is hbx_verify_sigs_keyed; `legacy` feeds the same items to hbx_verify_sigs with the keys
+gathered per item (the only path before the keyed call: the baseline); `both` alternates them, keyed
+first, two rounds in one process.  Every pass records wall time and the hbx_kernel_time sums of
+hash_nonces, decode_sigs and verify_sig (hbx_verify_sigs times only its check kernel: its hash, decode
+and line preparation show in its wall time alone).  Messages are --sig-msg-len seeded bytes each; a
+real Ack is N ciphertexts, about 190 N bytes.  The statuses must all be VALID and equal across paths.
+A pass that fails (device memory) or does not fit --limit-s is recorded as such.  --sigs-only skips the eras.
 """
 from __future__ import annotations
 
@@ -150,12 +163,75 @@ def era(ctx, n: int, seed: int = 1, deadline: float = None, ct_check: int = 0):
                                        "k_sk_decrypt": round(split["sk_decrypt"][0], 3)}}
 
 
+SIG_KERNELS = ("hash_nonces", "decode_sigs", "verify_sig")
+
+
+def sig_stages(ctx, n: int, msg_len: int, paths, rounds: int = 2, seed: int = 2, deadline: float = None):
+    """The era's signatures: N + 1 signed by this node, N + N^2 verified, `rounds` times per path."""
+    from hbbft_amd.hbx import HbxError
+
+    rng = np.random.default_rng(seed)
+    count = n + n * n
+    sk_nodes = _scalars(rng, n)
+    sk_nodes[:, 31] |= 1  # not zero
+    pk_nodes = ctx.public_keys(sk_nodes)
+    # item k is signed by node k % n: every node's Part, then its N Acks; N + 1 messages per node
+    blob = rng.integers(0, 256, size=count * msg_len, dtype=np.uint8).tobytes()
+    msgs = [blob[k * msg_len:(k + 1) * msg_len] for k in range(count)]
+    key_idx = (np.arange(count) % n).astype(np.uint32)
+    sig = np.zeros((count, 96), dtype=np.uint8)
+    out = {"n": n, "items": count, "keys": n, "msg_len": msg_len, "passes": []}
+    t0 = time.perf_counter()
+    for i in range(n):  # untimed but for node 0: the other nodes' signatures are inputs
+        mine = np.flatnonzero(key_idx == i)
+        t1 = time.perf_counter()
+        sig[mine] = ctx.sign_msgs(sk_nodes[i].tobytes(), [msgs[k] for k in mine])
+        if i == 0:
+            out["kg_sign_ms"] = round((time.perf_counter() - t1) * 1e3, 3)
+            out["kg_sign_msgs"] = len(mine)
+    out["inputs_s"] = round(time.perf_counter() - t0, 3)
+    pk_items = None
+    first = None
+    for r in range(rounds):
+        for path in paths:
+            rec = {"path": path, "round": r}
+            out["passes"].append(rec)
+            if deadline is not None and time.perf_counter() > deadline:
+                rec["skipped"] = "time limit"
+                continue
+            if path == "legacy" and pk_items is None:
+                pk_items = np.ascontiguousarray(pk_nodes[key_idx])
+            ctx.set_timing(True)
+            t1 = time.perf_counter()
+            try:
+                if path == "keyed":
+                    st, _ = ctx.verify_sigs_keyed(pk_nodes, key_idx, msgs, sig)
+                else:
+                    st = ctx.verify_sigs(pk_items, msgs, sig)
+            except HbxError as e:
+                ctx.set_timing(False)
+                rec["failed"] = str(e)
+                continue
+            rec["wall_ms"] = round((time.perf_counter() - t1) * 1e3, 3)
+            kt = {k: ctx.kernel_time(k) for k in SIG_KERNELS}
+            ctx.set_timing(False)
+            rec["kernel_ms"] = {k: round(v[0], 3) for k, v in kt.items()}
+            rec["kernel_sum_ms"] = round(sum(v[0] for v in kt.values()), 3)
+            assert (st == 1).all(), f"{path}: {int((st != 1).sum())} items not VALID"
+            first = st if first is None else first
+            assert (st == first).all()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=64)
     ap.add_argument("--try-256", action="store_true")
     ap.add_argument("--limit-s", type=float, default=240.0)
     ap.add_argument("--ct-check", choices=("wide", "pair", "both"), default="wide")
+    ap.add_argument("--sig-path", choices=("keyed", "legacy", "both"), default=None)
+    ap.add_argument("--sig-msg-len", type=int, default=64)
+    ap.add_argument("--sigs-only", action="store_true")
     args = ap.parse_args()
     from hbbft_amd.hbx import Context, build_info
 
@@ -167,12 +243,20 @@ def main():
     t0 = time.perf_counter()
     with Context(0) as ctx:
         try:
+            out = {"metric": "keygen_era", "lib": build_info()}
+            sig_paths = {None: [], "keyed": ["keyed"], "legacy": ["legacy"], "both": ["keyed", "legacy"]}[args.sig_path]
+            if sig_paths:
+                sig_stages(ctx, 4, args.sig_msg_len, sig_paths, rounds=1)  # warm-up
+                out["sigs"] = sig_stages(ctx, args.n, args.sig_msg_len, sig_paths)
+                if args.try_256:
+                    out["sigs_256"] = sig_stages(ctx, 256, args.sig_msg_len, sig_paths, deadline=t0 + args.limit_s)
+            if args.sigs_only:
+                modes = []
             for mode in modes:
                 era(ctx, 4, ct_check=mode)  # warm-up: module load, first allocations
-            out = {"metric": "keygen_era", "lib": build_info()}
             for mode in modes:
                 out[key("era", mode)] = era(ctx, args.n, ct_check=mode)
-            if args.try_256:
+            if args.try_256 and modes:
                 spent = time.perf_counter() - t0
                 # the whole N = 64 pass (inputs included, every mode) scaled by the N^2 stages' factor
                 predicted = spent * (256 / args.n) ** 2

@@ -554,4 +554,32 @@ int hc_ct_check_gen(const uint8_t* u48, const uint8_t* v, uint64_t len, const ui
   static uint32_t slot[LDS_FQ12D_DWORDS];
   return fq12d_is_one(final_exponentiation_d(f, slot)) ? 1 : 0;
 }
+// The pair-lane PublicKey::verify (k_verify_sigs2 + k_verify_sig_shares2_fe) of one item on one thread:
+// e(pk, H') e(-[m] g1, sigma) == 1 with H' = [m] hash_g2(msg) (k_hash_nonces with full = 0), both
+// pairs' lines generated on the fly.  The key's decode is the table's (G1 point or the identity);
+// sigma is decoded as a curve point only and its membership in G2 read from its own loop's
+// T = [|x|] sigma (g2_torsion_free_from_T), as lane 1 of the pair does.
+// 1 = verified, 0 = not, -1 = key or sigma undecodable (sigma off G2 included).
+int hc_sig_check_gen(const uint8_t* pk48, const uint8_t* msg, uint64_t len, const uint8_t* sig96, int digest) {
+  g1a P;
+  g2a S;
+  int32_t sp = g1_decompress_d(pk48, P);
+  if (sp == HBX_PT_OK && !g1_is_torsion_free_d(P)) sp = HBX_PT_NOT_IN_SUBGROUP;
+  const int32_t ss = g2_decompress(sig96, S);
+  if ((sp != HBX_PT_OK && sp != HBX_PT_INFINITY) || (ss != HBX_PT_OK && ss != HBX_PT_INFINITY)) return -1;
+  uint8_t d[32];
+  digest2(digest, msg, len, nullptr, 0, d);
+  const g2a Hp = g2_to_affine(g2_mul_bits(hash_g2_from_digest(d), HEFF_M, 256));
+  fq12d f = fq12d_one();
+  g2jd T;
+  if (!P.inf && !Hp.inf)  // a pairing with the identity contributes 1
+    f = miller_loop_gen_d(fq2d_from_fq2(Hp.x), fq2d_from_fq2(Hp.y), fqd_from_fq(P.x), fqd_from_fq(P.y), T);
+  if (!S.inf) {
+    f = fq12d_mul(f, miller_loop_gen_d(fq2d_from_fq2(S.x), fq2d_from_fq2(S.y), fqd_from_fq(fq_from_const(G1_MGEN_X)),
+                                       fqd_from_fq(fq_neg(fq_from_const(G1_MGEN_Y))), T));
+    if (!g2_torsion_free_from_T(T, S)) return -1;
+  }
+  static uint32_t slot[LDS_FQ12D_DWORDS];
+  return fq12d_is_one(final_exponentiation_d(f, slot)) ? 1 : 0;
+}
 }
