@@ -111,6 +111,82 @@ HBX_HDNI g1j g1d_mul_u128_w4(const g1a& P, const uint32_t* k4) {
   return g1j{fqd_to_fq(acc.x), fqd_to_fq(acc.y), fqd_to_fq(acc.z)};
 }
 
+// ---- Precomputed window tables for the threshold combine ---------------------------------------
+// The part of g1d_mul_u128_w4 that depends on the point alone, done once per share while the line
+// preparation leaves the chip idle (k_prepare_lines): D = [2^64] S and the 4-bit tables (1..15) S,
+// (1..15) D, Jacobian, relaxed digits.  [k] S = [k_lo] S + [k_hi] D is then one interleaved
+// (Straus) loop of 60 doublings and up to 32 table additions, against 14 + 124 + 31 operations.
+constexpr int G1D_TAB_N = 15;             // entries (1..15) P of one table
+constexpr int G1D_TABS = 2 * G1D_TAB_N;   // a share's entries at most: the table of D, then the table of S
+// What is precomputed per share (`form`), and the entries a share's slot then holds:
+//   0 = D and the table of D (15), the combine builds the table of S;
+//   1 = both tables by one lane (30);  2 = both, the table of S by a second set of lanes (30);
+//   3 = D alone (1), the combine builds both tables.
+HBX_HD uint32_t g1d_tab_stride(uint32_t form) { return form == 3 ? 1u : form == 0 ? (uint32_t)G1D_TAB_N : (uint32_t)G1D_TABS; }
+
+// tab[m - 1] = [m] P, m = 1..15: even multiples by doubling, odd ones as [m - 1] P + P.  P has
+// prime order r, so no addition meets equal or opposite points or the identity.
+HBX_HD void g1d_table15(const g1jd& P, g1jd* tab) {
+  tab[0] = P;
+  g1jd prev = P;
+#pragma unroll 1
+  for (int m = 2; m <= G1D_TAB_N; m++) {
+    prev = (m & 1) ? g1d_add_nc(prev, P) : g1d_dbl(tab[m / 2 - 1]);
+    tab[m - 1] = prev;
+  }
+}
+
+HBX_HDNI void g1d_table15_ni(const g1jd& P, g1jd* tab) { g1d_table15(P, tab); }
+
+// The tables of S (not the identity, of order r) into a slot T.  parts: bit 1 = D and the table
+// of D (T[0 .. 14]), bit 0 = the table of S (T[15 .. 29]), 4 = D alone (T[0]); the rest is left
+// untouched.
+HBX_HDNI void g1d_build_tables(const g1jd& S, g1jd* T, int parts) {
+  g1jd d = S;
+  if (parts & 6) {
+#pragma unroll 1
+    for (int i = 0; i < 64; i++) d = g1d_dbl(d);
+  }
+  if (parts & 4) T[0] = d;
+#pragma unroll 1
+  for (int h = 1; h >= 0; h--)
+    if (parts & (1 << h)) g1d_table15(h ? d : S, T + (h ? 0 : G1D_TAB_N));
+}
+
+// [k] S for the 128-bit k = k4 from the tables TS = (1..15) S and TD = (1..15) [2^64] S; with phi,
+// [k] phi(S) = phi([k] S) = (beta X, Y, Z).  The accumulator before a window's additions is
+// [16 a] S with a >= 1 (or the identity, a flag), the addends [n] S and [n 2^64] S with n <= 15:
+// 16 a + n_lo < 2^64 <= n_hi 2^64 and every sum stays below 2^129 < r, so no addition meets equal
+// or opposite points.  The same point as g1d_mul_u128_w4 (tests/test_combine_tables.py).
+HBX_HDNI g1j g1d_mul_u128_tab(const g1jd* TS, const g1jd* TD, const uint32_t* k4, bool phi) {
+  g1jd acc{fqd_const(FQD_ONE), fqd_const(FQD_ONE), fqd_zero()};
+  bool ai = true;
+#pragma unroll 1
+  for (int w = 15; w >= 0; w--) {
+    const uint32_t sh = (uint32_t)(w & 7) * 4;
+    const uint32_t nl = (k4[w >> 3] >> sh) & 0xFu, nh = (k4[2 + (w >> 3)] >> sh) & 0xFu;
+    // both entries are fetched ahead of the doublings, which hide the loads
+    const g1jd el = TS[nl ? nl - 1 : 0], eh = TD[nh ? nh - 1 : 0];
+    if (!ai) {
+#pragma unroll 1
+      for (int q = 0; q < 4; q++) acc = g1d_dbl(acc);
+    }
+    // (one copy of the addition for both tables: two would push this function past the reach
+    // of a short branch, tools/isa_check.py)
+#pragma unroll 1
+    for (int h = 0; h < 2; h++) {
+      if (h ? nh : nl) {
+        const g1jd& e = h ? eh : el;
+        acc = ai ? e : g1d_add_nc(acc, e);
+        ai = false;
+      }
+    }
+  }
+  if (ai) return g1_identity();
+  if (phi) acc.x = fqd_mul(acc.x, fqd_from_fq(fq_from_const(G1_BETA)));
+  return g1j{fqd_to_fq(acc.x), fqd_to_fq(acc.y), fqd_to_fq(acc.z)};
+}
+
 // P in G1 for an affine point on the curve (curve.hpp g1_is_torsion_free, the same criterion)
 HBX_HDNI bool g1_is_torsion_free_d(const g1a& P) {
   if (P.inf) return true;

@@ -28,6 +28,8 @@ namespace {
 // one wave per SIMD: a one-lane-per-check launch with fewer waves leaves SIMDs idle, and the
 // three-lane kernel finishes it sooner (MI355X: 256 CUs x 4 SIMDs)
 constexpr int VERIFY_FILL_WAVES = 1024;
+// the combine's precomputed tables: what k_prepare_lines' table lanes build (prepare_impl)
+constexpr uint32_t COMB_FORM = 1;
 
 struct dbuf {
   void* p = nullptr;
@@ -93,6 +95,15 @@ struct hbx_ctx {
   dbuf S, S_status, fallback, valid, shares_own, present_own, gslot;
   dbuf fe1slot;  // one-lane checks: the final exponentiation's global slots F, T, G (fe1d.hpp)
   uint32_t force_fallback = 0;  // hbx_debug_force_fallback (tests only)
+  // the combine's window tables (g1d.hpp; built by k_prepare_lines in the fused epoch call only):
+  // cap + 1 slots of G1D_TABS entries per proposer and their presence flags.  They belong to the
+  // shares decoded by the last fused prepare (tab_ready; dropped wherever n_shares is reset and
+  // when a verification decodes other shares into S).
+  int32_t comb_margin = HBX_COMBINE_MARGIN_AUTO;  // hbx_debug_set_combine_margin
+  dbuf comb_tab, comb_tab_ok, comb_slow;
+  bool tab_ready = false;
+  uint32_t comb_slow_p = 0;  // proposers of the last combine launch (entries of comb_slow)
+  uint32_t tab_cap = 0, tab_me = UINT32_MAX, tab_n = 0, tab_p = 0, tab_form = 0;
   // batched share verification (hbx_set_batch_verify): the seed, the index of the next batched
   // verification under it, and the p of the last verification if that one was batched (else 0);
   // key terms T[n + 1], ciphertext terms C[p], the sums Asum (affine) / AJ (Jacobian) / A / B [p],
@@ -642,7 +653,7 @@ int hbx_ctx_destroy(hbx_ctx* c) {
                   &c->vs_sig, &c->vs_sig_st, &c->vs_status, &c->fe1slot, &c->fb_lanes, &c->fb_coin, &c->fb_ct, &c->fb_sigs, &c->vk_pk48, &c->vk_pk, &c->vk_pkst, &c->vk_idx, &c->vk_gslot, &c->vk_sk, &c->hs[0], &c->hs[1], &c->hs[2], &c->hs[3], &c->hs[4], &c->hs[5], &c->coin_use, &c->bv_commit48, &c->bv_C, &c->bv_cst, &c->bv_rows,
                   &c->bv_rows48, &c->bv_pst, &c->bv_ackp, &c->bv_acky, &c->bv_vals, &c->bv_out,
                   &c->kg_sk, &c->kg_out, &c->kg_st, &c->b_seed, &c->b_AJ, &c->b_T, &c->b_C, &c->b_Asum, &c->b_A, &c->b_B,
-                  &c->b_cls0, &c->b_cand, &c->b_pass, &c->b_zero, &c->b_cls, &c->b_ctok, &c->b_stats, &c->rg_dev};
+                  &c->b_cls0, &c->b_cand, &c->b_pass, &c->b_zero, &c->b_cls, &c->b_ctok, &c->b_stats, &c->rg_dev, &c->comb_tab, &c->comb_tab_ok, &c->comb_slow};
   for (dbuf* b : bufs) b->release();
   if (c->rg_pin) (void)hipHostFree(c->rg_pin);
   if (c->rg_ev) (void)hipEventDestroy(c->rg_ev);
@@ -661,6 +672,7 @@ int hbx_set_digest(hbx_ctx* c, int variant) {
   c->ct_known = false;
   c->n_shares = 0;
   c->verified_p = 0;
+  c->tab_ready = false;
   c->coin_I = 0;
   c->coin_n = 0;
   return HBX_OK;
@@ -698,6 +710,44 @@ int64_t hbx_get_fallback_lanes(hbx_ctx* c) {
   uint32_t v = 0;
   HIPCHK(c, hipMemcpy(&v, c->fb_last->p, 4, hipMemcpyDeviceToHost));
   return v;
+}
+
+int hbx_debug_set_combine_margin(hbx_ctx* c, int32_t margin) {
+  if (!c || margin < HBX_COMBINE_TABLES_OFF)
+    return fail(c, HBX_E_INVALID_ARG, "hbx_debug_set_combine_margin: margin >= 0, AUTO or TABLES_OFF, not %d", margin);
+  c->comb_margin = margin;
+  return HBX_OK;
+}
+
+int64_t hbx_get_combine_slow_terms(hbx_ctx* c) {
+  if (!c) return HBX_E_INVALID_ARG;
+  if (!c->comb_slow.p || c->comb_slow_p == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, quiesce(c));
+  std::vector<uint32_t> v(c->comb_slow_p);
+  HIPCHK(c, hipMemcpy(v.data(), c->comb_slow.p, v.size() * 4, hipMemcpyDeviceToHost));
+  int64_t sum = 0;
+  for (uint32_t x : v) sum += x;
+  return sum;
+}
+
+// The combine's launch shape: a quad of lanes per GLV term over one-wave blocks (k_combine_q) when
+// that still leaves at most one wave per SIMD (an epoch shard), else one lane per term in one block
+// per proposer (k_combine, the only one that reads the window tables).
+static bool combine_quads(const hbx_ctx* c, uint32_t t, uint32_t p) {
+  const uint32_t nb = (2 * t + COMBQ_TERMS - 1) / COMBQ_TERMS;
+  return c->combine_lanes == 4 ? nb <= 16
+         : c->combine_lanes == 1 ? false
+                                 : nb <= 16 && (size_t)nb * p <= (size_t)VERIFY_FILL_WAVES;
+}
+
+// Senders per proposer whose window tables the fused epoch call precomputes (0: none): the first
+// t valid senders lie below t + margin unless more than `margin` of them are invalid.  The default
+// margin rounds t + 32 up to a whole wave of lanes.
+static uint32_t combine_tab_cap(const hbx_ctx* c, uint32_t n, uint32_t t, uint32_t p) {
+  if (c->comb_margin == HBX_COMBINE_TABLES_OFF || combine_quads(c, t, p)) return 0;
+  const uint64_t want = c->comb_margin >= 0 ? (uint64_t)t + (uint32_t)c->comb_margin : ((uint64_t)t + 32 + 63) / 64 * 64;
+  return (uint32_t)std::min<uint64_t>(n, want);
 }
 
 int hbx_set_batch_verify(hbx_ctx* c, const uint8_t* seed32) {
@@ -774,6 +824,7 @@ int hbx_set_pk_shares(hbx_ctx* c, const uint8_t* pk_comp, uint32_t n, int32_t* s
   c->ct_known = false;
   c->n_shares = 0;
   c->verified_p = 0;
+  c->tab_ready = false;
   c->coin_n = 0;
   if (!c->pk.ensure((size_t)n * sizeof(g1a)) || !c->pk_m.ensure((size_t)n * sizeof(g1a)) ||
       !c->pk64.ensure((size_t)n * sizeof(g1a)) || !c->pk_status.ensure((size_t)n * 4) || !c->pk_comp.ensure((size_t)n * 48))
@@ -875,7 +926,7 @@ static int launch_prepare_ct(hbx_ctx* c, hipStream_t s, const uint8_t* d_u_comp,
 // epoch are decoded in the same launch, in waves beside the hash chains.
 static int prepare_impl(hbx_ctx* c, const uint8_t* d_u_comp, const uint8_t* d_v_blob, const uint64_t* d_v_off,
                         const uint8_t* d_w_comp, uint32_t p, uint64_t max_v_len, uint8_t* d_ct_valid,
-                        void* stream, const uint8_t* early_shares, uint32_t early_n) {
+                        void* stream, const uint8_t* early_shares, uint32_t early_n, uint32_t tab_cap = 0) {
   if (!c || p == 0 || !d_u_comp || !d_v_off || !d_w_comp)
     return fail(c, HBX_E_INVALID_ARG, "hbx_prepare_ciphertexts_d: bad args");
   HIPCHK(c, hipSetDevice(c->device));
@@ -889,6 +940,15 @@ static int prepare_impl(hbx_ctx* c, const uint8_t* d_u_comp, const uint8_t* d_v_
   const size_t m_early = early_shares ? (size_t)early_n * p : 0;
   if (m_early && (!c->S.ensure(m_early * sizeof(g1a)) || !c->S_status.ensure(m_early * 4)))
     return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_prepare_ciphertexts_d: out of device memory");
+  // What the table lanes precompute (g1d.hpp g1d_tab_stride): HBX_COMB_FORM=0..3 (profiling)
+  // overrides the default; DESIGN.md section 5 records what each form measured.
+  static const char* form_env = getenv("HBX_COMB_FORM");
+  const uint32_t form = form_env && form_env[0] >= '0' && form_env[0] <= '3' ? (uint32_t)(form_env[0] - '0') : COMB_FORM;
+  c->tab_ready = false;
+  if (!m_early) tab_cap = 0;
+  if (tab_cap && (!c->comb_tab.ensure((size_t)p * (tab_cap + 1) * g1d_tab_stride(form) * sizeof(g1jd)) ||
+                  !c->comb_tab_ok.ensure((size_t)p * (tab_cap + 1))))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_decrypt_epoch_d: out of device memory for the combine's tables");
   const dim3 b64(64);
   const bool own = c->own_me != UINT32_MAX;
   // own entry of the early-decoded matrix (written by k_prepare_lines), as hbx_verify_dec_shares_d
@@ -899,6 +959,11 @@ static int prepare_impl(hbx_ctx* c, const uint8_t* d_u_comp, const uint8_t* d_v_
     timed t_(c, HBX_K_PREPARE_LINES, s);
     const uint32_t line_blocks = (2 * p * LINE_K + 63) / 64, own_blocks = own ? (p + 63) / 64 : 0;
     const bool own_entry = m_early && me_early != UINT32_MAX;
+    // the combine's window tables in further blocks of this launch (k_prepare_lines): with the
+    // default cap at N = 256, 512 waves beside the 128 line waves and the own-share waves, still
+    // at most one wave per SIMD
+    const uint32_t tab_blocks =
+        tab_cap ? (form == 2 ? 2 : 1) * ((own_entry ? own_blocks : 0) + (uint32_t)(((size_t)p * tab_cap + 63) / 64)) : 0;
     // grouped addition steps (g2_raw_lines_group<true>) at every size: since the group rounds pick
     // their operands by blocks (groupd.hpp gd_round) the grouped kernel is the faster one at N=256
     // too (lines 1.00 -> 0.85 ms, epoch 23.43 -> 23.27 ms averaged over two runs each), and two
@@ -906,12 +971,13 @@ static int prepare_impl(hbx_ctx* c, const uint8_t* d_u_comp, const uint8_t* d_v_
     // had kept it to launches below a full chip: its register footprint then slowed two epochs in
     // flight 28.2 -> 32.5 ms per epoch (profiles/r03n_bisect_*).
     auto kpl = k_prepare_lines<true>;
-    hipLaunchKernelGGL(kpl, dim3(line_blocks + own_blocks), b64, 0, s, c->G2pts.as<g2a>(), 2 * p,
+    hipLaunchKernelGGL(kpl, dim3(line_blocks + own_blocks + tab_blocks), b64, 0, s, c->G2pts.as<g2a>(), 2 * p,
                        c->lines_d.as<line_pre_d>(), c->scratch.as<fq2d>(), c->dec_st.as<int32_t>(), p,
                        c->ct_ok.as<uint8_t>(), own ? c->own_part.as<g1j>() : nullptr,
                        own ? c->own_S.as<g1a>() : nullptr, early_n, me_early,
                        own_entry ? c->S.as<g1a>() : nullptr, own_entry ? c->S_status.as<int32_t>() : nullptr,
-                       c->Hj.as<g2j>());
+                       c->Hj.as<g2j>(), c->S.as<g1a>(), c->S_status.as<int32_t>(),
+                       tab_cap ? c->comb_tab.as<g1jd>() : nullptr, c->comb_tab_ok.as<uint8_t>(), tab_cap, form);
     HIPCHK(c, hipGetLastError());
     const uint32_t nl = 2 * p * MILLER_LINES;
     hipLaunchKernelGGL(k_normalise_lines, dim3((nl + 63) / 64), b64, 0, s, c->lines.as<line_pre>(),
@@ -923,6 +989,12 @@ static int prepare_impl(hbx_ctx* c, const uint8_t* d_u_comp, const uint8_t* d_v_
   c->ct_known = false;
   c->n_shares = 0;  // S / valid of an earlier verify belong to other ciphertexts
   c->verified_p = 0;
+  c->tab_ready = tab_cap != 0;  // tables of an earlier fused call belong to other shares
+  c->tab_cap = tab_cap;
+  c->tab_me = me_early;
+  c->tab_n = early_n;
+  c->tab_p = p;
+  c->tab_form = form;
   if (d_ct_valid) {
     // Ciphertext::verify now: one check per proposer (n = 0 share jobs, job 0 = the ciphertext)
     if (!c->S.ensure(sizeof(g1a)) || !c->S_status.ensure(4) || !c->valid.ensure(16))
@@ -992,6 +1064,7 @@ static int verify_impl(hbx_ctx* c, const uint8_t* d_shares, const uint8_t* d_pre
   // Ciphertext::verify (k_verify_shares); otherwise the ciphertext checks run separately
   const bool own = c->own_ready && c->own_me < n;
   if (!predecoded) {
+    c->tab_ready = false;  // S is about to hold other shares than the tables were made from
     hipLaunchKernelGGL(k_decompress_shares, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, d_shares, m,
                        c->S.as<g1a>(), c->S_status.as<int32_t>(), n, own ? c->own_me : UINT32_MAX,
                        own ? c->own_S.as<g1a>() : nullptr);
@@ -1961,7 +2034,7 @@ static int verify_sig_impl(hbx_ctx* c, const uint8_t* d_sig96, const uint8_t* d_
     timed t_(c, HBX_K_PREPARE_LINES, s);
     hipLaunchKernelGGL(k_prepare_lines<true>, dim3((count * LINE_K + 63) / 64), dim3(64), 0, s, c->coin_Hp.as<g2a>(), count,
                        c->coin_lines_d.as<line_pre_d>(), c->coin_scratch.as<fq2d>(), nullptr, 0u, nullptr, nullptr, nullptr, 1u,
-                       UINT32_MAX, nullptr, nullptr, nullptr);
+                       UINT32_MAX, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0u);
     HIPCHK(c, hipGetLastError());
     const uint32_t nl = count * MILLER_LINES;
     hipLaunchKernelGGL(k_normalise_lines, dim3((nl + 63) / 64), dim3(64), 0, s, c->coin_lines.as<line_pre>(),
@@ -2090,7 +2163,7 @@ int hbx_verify_sigs(hbx_ctx* c, const uint8_t* pk48, const uint8_t* msg_blob, co
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(k_prepare_lines<true>, dim3((count * LINE_K + 63) / 64), dim3(64), 0, s, c->vs_H.as<g2a>(), count,
                      c->vs_lines_d.as<line_pre_d>(), c->vs_scratch.as<fq2d>(), nullptr, 0u, nullptr, nullptr, nullptr, 1u,
-                     UINT32_MAX, nullptr, nullptr, nullptr);
+                     UINT32_MAX, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0u);
   HIPCHK(c, hipGetLastError());
   const uint32_t nl = count * MILLER_LINES;
   hipLaunchKernelGGL(k_normalise_lines, dim3((nl + 63) / 64), dim3(64), 0, s, c->vs_lines.as<line_pre>(),
@@ -2412,20 +2485,24 @@ int hbx_combine_decrypt_d(hbx_ctx* c, uint32_t t, uint8_t* d_out_blob, int32_t* 
     // a quad of lanes per GLV term over one-wave blocks when that still leaves at most one wave per
     // SIMD (an epoch shard; k_combine_q), else one lane per term in one block per proposer
     const uint32_t nb = (2 * t + COMBQ_TERMS - 1) / COMBQ_TERMS;
-    const bool quads = c->combine_lanes == 4 ? nb <= 16
-                       : c->combine_lanes == 1 ? false
-                                               : nb <= 16 && (size_t)nb * p <= (size_t)VERIFY_FILL_WAVES;
+    const bool quads = combine_quads(c, t, p);
+    // terms without tables, counted per proposer (every block writes its entry)
+    if (!c->comb_slow.ensure((size_t)p * 4)) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_combine_decrypt_d: out of device memory");
+    c->comb_slow_p = p;
+    // window tables of the last fused prepare, if they are of these shares
+    const bool tabs = c->tab_ready && c->tab_n == c->n_shares && c->tab_p == p;
     if (quads) {
       if (!c->comb_partial.ensure((size_t)p * nb * sizeof(g1j)) || !c->comb_done.ensure((size_t)p * 4))
         return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_combine_decrypt_d: out of device memory");
       HIPCHK(c, hipMemsetAsync(c->comb_done.p, 0, (size_t)p * 4, s));
       hipLaunchKernelGGL(k_combine_q, dim3(nb, p), dim3(64), 0, s, c->valid.as<uint8_t>(), c->S.as<g1a>(),
                          c->n_shares, t, c->ct_valid.as<uint8_t>(), c->keys.as<uint32_t>(), c->status.as<int32_t>(),
-                         c->digest, c->comb_partial.as<g1j>(), c->comb_done.as<uint32_t>());
+                         c->digest, c->comb_partial.as<g1j>(), c->comb_done.as<uint32_t>(), c->comb_slow.as<uint32_t>());
     } else
     hipLaunchKernelGGL(k_combine, dim3(p), dim3(COMBINE_THREADS), 0, s, c->valid.as<uint8_t>(), c->S.as<g1a>(),
                        c->n_shares, t, c->ct_valid.as<uint8_t>(), c->keys.as<uint32_t>(), c->status.as<int32_t>(),
-                       c->digest);
+                       c->digest, tabs ? c->comb_tab.as<g1jd>() : nullptr, c->comb_tab_ok.as<uint8_t>(),
+                       tabs ? c->tab_cap : 0u, c->tab_me, c->tab_form, c->comb_slow.as<uint32_t>());
   }
   HIPCHK(c, hipGetLastError());
   const uint64_t blocks = (c->max_v_len + 15) / 16;
@@ -2448,7 +2525,10 @@ int hbx_decrypt_epoch_d(hbx_ctx* c, const uint8_t* d_u_comp, const uint8_t* d_v_
   // Stages in stream order.  (Running Ciphertext::verify on the aux stream beside a speculative
   // combine was measured on MI355X and gained nothing: the combine's 4 waves per proposer already
   // occupy every SIMD, and two single-wave-per-SIMD kernels only time-share the VALU.)
-  int rc = prepare_impl(c, d_u_comp, d_v_blob, d_v_off, d_w_comp, p, max_v_len, nullptr, stream, d_shares, n);
+  // The combine's window tables are made beside the line preparation, whose chains leave most of
+  // the chip idle (k_prepare_lines); the combine falls back per term where a table is missing.
+  int rc = prepare_impl(c, d_u_comp, d_v_blob, d_v_off, d_w_comp, p, max_v_len, nullptr, stream, d_shares, n,
+                        combine_tab_cap(c, n, t, p));
   if (rc) return rc;
   rc = verify_impl(c, d_shares, d_present, n, p, d_valid, stream, true);
   if (rc) return rc;
@@ -2816,6 +2896,7 @@ int hbx_sk_decrypt(hbx_ctx* c, const uint8_t* sk32, const uint8_t* u48, const ui
   c->ct_known = false;
   c->n_shares = 0;
   c->verified_p = 0;
+  c->tab_ready = false;
   if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(status, c->kg_st.p, count, hipMemcpyDeviceToHost, s));
   if (total) HIPCHK(c, hipMemcpyAsync(out_blob, c->kg_out.p, total, hipMemcpyDeviceToHost, s));

@@ -221,11 +221,60 @@ __global__ void __launch_bounds__(64) k_prepare_lines(g2a* __restrict__ pts, uin
                                                       uint8_t* __restrict__ ct_ok, const g1j* __restrict__ own_part,
                                                       g1a* __restrict__ own_S, uint32_t n, uint32_t me,
                                                       g1a* __restrict__ S, int32_t* __restrict__ S_status,
-                                                      const g2j* __restrict__ Hj) {
+                                                      const g2j* __restrict__ Hj, const g1a* __restrict__ tab_S,
+                                                      const int32_t* __restrict__ tab_S_status,
+                                                      g1jd* __restrict__ tabs, uint8_t* __restrict__ tab_ok,
+                                                      uint32_t cap, uint32_t form) {
   const uint32_t line_blocks = (count * LINE_K + 63) / 64;
   if (blockIdx.x >= line_blocks) {
+    uint32_t b = blockIdx.x - line_blocks;
+    const uint32_t own_blocks = own_part ? (p + 63) / 64 : 0;
+    if (b >= own_blocks) {
+      // The combine's window tables (g1d.hpp g1d_build_tables), in blocks of their own beside the
+      // line chains, which leave most SIMDs idle: one lane per (proposer j, sender i < cap) whose
+      // share decoded (k_prepare_ct), into slot i of proposer j's cap + 1 slots.  The own share
+      // is written by the own-share blocks of this launch, so its tables come from lanes of their
+      // own, which add the two halves again and take the Jacobian sum (slot me, or slot cap for
+      // me >= cap).  tab_ok says which slots hold tables.  `form` (g1d.hpp g1d_tab_stride) says
+      // how much of them is made here; form 2's second set of lanes comes in blocks after the first.
+      if (!tabs) return;
+      b -= own_blocks;
+      const uint32_t slots = cap + 1;
+      const uint32_t own_tab_blocks = (own_part && me != UINT32_MAX) ? own_blocks : 0;
+      const uint32_t set_blocks = own_tab_blocks + (uint32_t)(((size_t)p * cap + 63) / 64);
+      const bool second = b >= set_blocks;  // form 2's lanes for the table of S
+      if (second) b -= set_blocks;
+      const int parts = second ? 1 : form == 1 ? 3 : form == 3 ? 4 : 2;
+      const uint32_t stride = g1d_tab_stride(form);
+      if (b < own_tab_blocks) {
+        const uint32_t j = b * blockDim.x + threadIdx.x;
+        if (j >= p) return;
+        const size_t slot = (size_t)j * slots + (me < cap ? me : cap);
+        bool ok = false;
+        if (dec_st[j] == HBX_PT_OK) {
+          const g1j sum = g1_add(own_part[2 * j], own_part[2 * j + 1]);
+          if (!g1j_is_identity(sum)) {
+            g1d_build_tables(g1jd{fqd_from_fq(sum.x), fqd_from_fq(sum.y), fqd_from_fq(sum.z)}, tabs + slot * stride, parts);
+            ok = true;
+          }
+        }
+        if (!second) tab_ok[slot] = ok ? 1 : 0;
+        return;
+      }
+      b -= own_tab_blocks;
+      const size_t e = (size_t)b * blockDim.x + threadIdx.x;
+      if (e >= (size_t)p * cap) return;
+      const uint32_t j = (uint32_t)(e / cap), i = (uint32_t)(e % cap);
+      if (i == me) return;
+      const size_t slot = (size_t)j * slots + i;
+      const g1a sp = tab_S[(size_t)j * n + i];
+      const bool ok = tab_S_status[(size_t)j * n + i] == HBX_PT_OK && !sp.inf;
+      if (ok) g1d_build_tables(g1jd{fqd_from_fq(sp.x), fqd_from_fq(sp.y), fqd_const(FQD_ONE)}, tabs + slot * stride, parts);
+      if (!second) tab_ok[slot] = ok ? 1 : 0;
+      return;
+    }
     // own share S_j,me = k1 U_j + k2 phi(U_j) (k_prepare_ct's two halves) where U_j decoded
-    const uint32_t j = (blockIdx.x - line_blocks) * blockDim.x + threadIdx.x;
+    const uint32_t j = b * blockDim.x + threadIdx.x;
     if (j >= p) return;
     g1a sh;
     sh.x = fq_zero();
@@ -279,9 +328,11 @@ __global__ void __launch_bounds__(64) k_prepare_lines(g2a* __restrict__ pts, uin
                             scratch + (size_t)k * MILLER_LINES, gl);
 }
 template __global__ void k_prepare_lines<true>(g2a*, uint32_t, line_pre_d*, fq2d*, const int32_t*, uint32_t, uint8_t*,
-                                               const g1j*, g1a*, uint32_t, uint32_t, g1a*, int32_t*, const g2j*);
+                                               const g1j*, g1a*, uint32_t, uint32_t, g1a*, int32_t*, const g2j*, const g1a*,
+                                               const int32_t*, g1jd*, uint8_t*, uint32_t, uint32_t);
 template __global__ void k_prepare_lines<false>(g2a*, uint32_t, line_pre_d*, fq2d*, const int32_t*, uint32_t, uint8_t*,
-                                                const g1j*, g1a*, uint32_t, uint32_t, g1a*, int32_t*, const g2j*);
+                                                const g1j*, g1a*, uint32_t, uint32_t, g1a*, int32_t*, const g2j*, const g1a*,
+                                               const int32_t*, g1jd*, uint8_t*, uint32_t, uint32_t);
 
 // Second half of the line preparation: one lane per raw line, (c0, c1) /= c2.  68 independent
 // Fq2 inversions replace the batched inversion (3 x 68 Fq2 products plus one inversion) that
@@ -818,15 +869,21 @@ __global__ void __launch_bounds__(COMBINE_THREADS) k_combine(const uint8_t* __re
                                                              const g1a* __restrict__ S, uint32_t n,
                                                              uint32_t t, const uint8_t* __restrict__ ct_valid,
                                                              uint32_t* __restrict__ keys,
-                                                             int32_t* __restrict__ status, int digest) {
+                                                             int32_t* __restrict__ status, int digest,
+                                                             const g1jd* __restrict__ tabs,
+                                                             const uint8_t* __restrict__ tab_ok, uint32_t cap,
+                                                             uint32_t tab_me, uint32_t form,
+                                                             uint32_t* __restrict__ slow) {
   __shared__ uint16_t idx[COMBINE_MAX_T];
   __shared__ int wcnt[COMBINE_THREADS / 64];
   __shared__ fr xm[COMBINE_LDS_T];  // Montgomery x_k = idx_k + 1 (t <= COMBINE_LDS_T)
   __shared__ fr nall;               // prod_k x_k
   __shared__ fr tp[COMBINE_LDS_T];  // its product tree
   __shared__ g1j red[COMBINE_THREADS];
+  __shared__ uint32_t slow_cnt;  // terms of this proposer without tables (slow[j])
   const uint32_t j = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (tid == 0) slow_cnt = 0;
   // the first t valid senders in index order (BTreeMap order, honey_badger.rs:328-340): a
   // block-wide ballot compaction, 256 senders per step
   int count = 0;
@@ -848,7 +905,10 @@ __global__ void __launch_bounds__(COMBINE_THREADS) k_combine(const uint8_t* __re
   }
   const bool ctv = ct_valid[j] == HBX_CT_VALID;
   if (!ctv || count < (int)t) {
-    if (tid == 0) status[j] = !ctv ? -7 : -3;
+    if (tid == 0) {
+      status[j] = !ctv ? -7 : -3;
+      slow[j] = 0;
+    }
     return;
   }
   // Lagrange numerators shared through LDS: lambda_k = N / (x_k prod_{m != k} (x_m - x_k)) with
@@ -898,7 +958,25 @@ __global__ void __launch_bounds__(COMBINE_THREADS) k_combine(const uint8_t* __re
     }
     uint32_t k1[4], k2[4];
     g1_glv_split(lam.l, k1, k2);
-    g1a sp = S[(size_t)j * n + idx[k]];
+    // the share's window tables where k_prepare_lines built them (slot i < cap, or slot cap for
+    // the own share of a node me >= cap): the interleaved loop over lambda's half, phi applied to
+    // the result; every other term multiplies from the point as before
+    const uint32_t i = idx[k];
+    const uint32_t slot = i < cap ? i : (i == tab_me ? cap : UINT32_MAX);
+    const size_t ts = (size_t)j * (cap + 1) + slot;
+    g1a sp = S[(size_t)j * n + i];
+    if (tabs && slot != UINT32_MAX && tab_ok[ts]) {
+      // the slot holds both tables, or the table of D, or D alone (g1d_tab_stride): the rest is
+      // built here, in this lane's scratch
+      const g1jd* T = tabs + ts * g1d_tab_stride(form);
+      g1jd TS[G1D_TAB_N], TD[G1D_TAB_N];
+      const bool have_s = form == 1 || form == 2, have_d = form != 3;
+      if (!have_s) g1d_table15_ni(g1jd{fqd_from_fq(sp.x), fqd_from_fq(sp.y), fqd_const(FQD_ONE)}, TS);
+      if (!have_d) g1d_table15_ni(T[0], TD);
+      acc = g1_add(acc, g1d_mul_u128_tab(have_s ? T + G1D_TAB_N : TS, have_d ? T : TD, (q & 1) ? k2 : k1, (q & 1) != 0));
+      continue;
+    }
+    atomicAdd(&slow_cnt, 1u);
     if (q & 1) sp.x = fq_mul(sp.x, fq_from_const(G1_BETA));
     acc = g1_add(acc, g1d_mul_u128_w4(sp, (q & 1) ? k2 : k1));  // digit tower (g1d.hpp)
   }
@@ -909,6 +987,7 @@ __global__ void __launch_bounds__(COMBINE_THREADS) k_combine(const uint8_t* __re
     __syncthreads();
   }
   if (tid == 0) {
+    slow[j] = slow_cnt;
     const g1a g = g1_to_affine(red[0]);
     uint8_t comp[48], d[32];
     g1_compress(g, comp);
@@ -942,7 +1021,7 @@ __global__ void __launch_bounds__(64, 1) k_combine_q(const uint8_t* __restrict__
                                                      uint32_t n, uint32_t t, const uint8_t* __restrict__ ct_valid,
                                                      uint32_t* __restrict__ keys, int32_t* __restrict__ status,
                                                      int digest, g1j* __restrict__ partial,
-                                                     uint32_t* __restrict__ done) {
+                                                     uint32_t* __restrict__ done, uint32_t* __restrict__ slow) {
   __shared__ uint16_t idx[COMBINE_LDS_T];
   __shared__ fr xm[COMBINE_LDS_T];
   __shared__ uint32_t lk[COMBQ_TERMS / 2][8];
@@ -960,7 +1039,10 @@ __global__ void __launch_bounds__(64, 1) k_combine_q(const uint8_t* __restrict__
   }
   const bool ctv = ct_valid[j] == HBX_CT_VALID;
   if (!ctv || count < (int)t) {
-    if (b == 0 && lane == 0) status[j] = !ctv ? -7 : -3;
+    if (b == 0 && lane == 0) {
+      status[j] = !ctv ? -7 : -3;
+      slow[j] = 0;
+    }
     return;  // every block of the proposer returns here: the counter is untouched
   }
   __syncthreads();
@@ -1046,6 +1128,7 @@ __global__ void __launch_bounds__(64, 1) k_combine_q(const uint8_t* __restrict__
   for (int m = 4; m < 64; m <<= 1) tot = g1_add_q4(tot, g1j_shfl_xor_q(tot, m), s);
   if (lane == 0) {
     done[j] = 0;  // ready for the next launch
+    slow[j] = 2 * t;  // no table path here: every term multiplies from the point
     const g1a g = g1_to_affine(tot);
     uint8_t comp[48], d[32];
     g1_compress(g, comp);

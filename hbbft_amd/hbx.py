@@ -77,6 +77,8 @@ EXPORTS = (
     "hbx_set_combine_lanes",
     "hbx_debug_force_fallback",
     "hbx_get_fallback_lanes",
+    "hbx_debug_set_combine_margin",
+    "hbx_get_combine_slow_terms",
     "hbx_build_id",
     "hbx_merkle_node_count",
     "hbx_merkle_build_d",
@@ -129,6 +131,9 @@ CT_UNDECODABLE = 3
 # line tables (default), or one lane pair per ciphertext
 CT_CHECK_WIDE = 0
 CT_CHECK_PAIR = 1
+# hbx_debug_set_combine_margin (include/hbx.h HBX_COMBINE_*)
+COMBINE_MARGIN_AUTO = -1
+COMBINE_TABLES_OFF = -2
 # ciphertexts per pass of hbx_sk_decrypt in pair mode (hbbft_amd/csrc/hbx_api.hip SK_DECRYPT_PAIR_CHUNK)
 SK_DECRYPT_PAIR_CHUNK = 16384
 # items per pass of hbx_verify_sigs_keyed / hbx_sign_msgs (hbbft_amd/csrc/hbx_api.hip VERIFY_SIGS_CHUNK)
@@ -225,6 +230,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.hbx_debug_force_fallback.argtypes = [P, u32]
     lib.hbx_get_fallback_lanes.argtypes = [P]
     lib.hbx_get_fallback_lanes.restype = ctypes.c_int64
+    lib.hbx_debug_set_combine_margin.argtypes = [P, ctypes.c_int32]
+    lib.hbx_get_combine_slow_terms.argtypes = [P]
+    lib.hbx_get_combine_slow_terms.restype = ctypes.c_int64
     lib.hbx_merkle_node_count.argtypes = [u32]
     lib.hbx_merkle_node_count.restype = u32
     lib.hbx_merkle_build_d.argtypes = [P, P, u32, u32, u32, P, P, P]
@@ -410,6 +418,19 @@ class Context:
     def set_combine_lanes(self, lanes: int):
         """hbx_set_combine_lanes: 0 auto (default), 1 (a lane per Lagrange term) or 4 (a quad per term)."""
         self._check(self.lib.hbx_set_combine_lanes(self.h, lanes))
+
+    def debug_set_combine_margin(self, margin: int):
+        """hbx_debug_set_combine_margin (tests only): the fused epoch call precomputes the combine's
+        window tables for senders below ``t + margin``; ``COMBINE_MARGIN_AUTO`` (default) or
+        ``COMBINE_TABLES_OFF``."""
+        self._check(self.lib.hbx_debug_set_combine_margin(self.h, margin))
+
+    def combine_slow_terms(self) -> int:
+        """hbx_get_combine_slow_terms: GLV half-terms of the last combine that had no tables."""
+        v = int(self.lib.hbx_get_combine_slow_terms(self.h))
+        if v < 0:
+            self._check(v)
+        return v
 
     def set_merkle_digest(self, variant: int):
         """hbx_set_merkle_digest: MERKLE_SHA256 (default, afck merkle) or MERKLE_SHA3."""

@@ -176,6 +176,23 @@ int64_t hbx_get_fallback_lanes(hbx_ctx* ctx);
  * one-wave blocks (k_combine_q, t <= 128), 0 = by launch size (default: 4 when the quad blocks fit
  * in 1024 waves, else 1). */
 int hbx_set_combine_lanes(hbx_ctx* ctx, int lanes);
+/* The combine's precomputed window tables (no reference counterpart; results identical).
+ * hbx_decrypt_epoch_d, when its combine runs one lane per term, has the line-preparation launch
+ * also compute, for every proposer and every sender i < cap = min(n, t + margin) whose share
+ * decoded (and for this node's own share), D = [2^64] S and the 4-bit tables of S and D; the
+ * combine's lanes then run one interleaved loop from those tables instead of a 128-bit window
+ * multiplication from the point.  A term without tables -- a sender at or beyond cap, the
+ * three-call API, the quad combine -- multiplies from the point as before.  The table buffer is
+ * allocated by the fused call only: p x (cap + 1) x 5,040 bytes.
+ * hbx_debug_set_combine_margin (tests only): margin >= 0, HBX_COMBINE_MARGIN_AUTO (default: cap
+ * = t + 32 rounded up to a multiple of 64) or HBX_COMBINE_TABLES_OFF (no tables at all).
+ * hbx_get_combine_slow_terms: GLV half-terms of the last combine launch that multiplied from the
+ * point (every term of a quad combine; 0 for an honest epoch at the default margin).  Read it
+ * after the launch it asks about, as hbx_get_fallback_lanes. */
+#define HBX_COMBINE_MARGIN_AUTO (-1)
+#define HBX_COMBINE_TABLES_OFF (-2)
+int hbx_debug_set_combine_margin(hbx_ctx* ctx, int32_t margin);
+int64_t hbx_get_combine_slow_terms(hbx_ctx* ctx);
 /* Batched decryption-share verification by random linear combination (no reference counterpart;
  * statuses identical except with probability <= 2^-128 per column, DESIGN.md "Batched share
  * verification").  seed32 != NULL: hbx_verify_dec_shares[_d] and hbx_decrypt_epoch_d decide each

@@ -406,6 +406,44 @@ int hc_g1_mul_u128_cmp(const uint8_t* p48, const uint32_t* k4) {
   if (a.inf || b.inf) return a.inf == b.inf ? 1 : 0;
   return fq_eq(a.x, b.x) && fq_eq(a.y, b.y) ? 1 : 0;
 }
+// the combine's table path (g1d.hpp g1d_build_tables + g1d_mul_u128_tab) against g1d_mul_u128_w4
+// and the 12-limb g1_mul_u128_w4, for P and for phi(P), with the tables built from the affine point
+// and from a Jacobian form of it (Z = z0 != 1, the own share's case), and with the table of S
+// built apart (parts = 2) or both (parts = 4, from D alone).  1 = all agree, 0 = not, -1 = P does not decode; the identity has
+// no tables (the kernels leave it to g1d_mul_u128_w4): 2 if that returns the identity.
+int hc_g1_mul_u128_tab_cmp(const uint8_t* p48, const uint32_t* k4, uint64_t z0) {
+  g1a P;
+  const int32_t st = g1_decompress(p48, P);
+  if (st == HBX_PT_INFINITY) return g1j_is_identity(g1d_mul_u128_w4(P, k4)) ? 2 : 0;
+  if (st != HBX_PT_OK) return -1;
+  auto same = [](const g1j& u, const g1j& v) {
+    const g1a a = g1_to_affine(u), b = g1_to_affine(v);
+    if (a.inf || b.inf) return a.inf == b.inf;
+    return fq_eq(a.x, b.x) && fq_eq(a.y, b.y);
+  };
+  g1a Q = P;
+  Q.x = fq_mul(Q.x, fq_from_const(G1_BETA));
+  const g1j want = g1_mul_u128_w4(P, k4), want_phi = g1_mul_u128_w4(Q, k4);
+  if (!same(want, g1d_mul_u128_w4(P, k4)) || !same(want_phi, g1d_mul_u128_w4(Q, k4))) return 0;
+  fq z{};
+  z.l[0] = (uint32_t)z0;
+  z.l[1] = (uint32_t)(z0 >> 32);
+  z = fq_to_mont(z);
+  const fq z2 = fq_sqr(z);
+  const g1jd aff{fqd_from_fq(P.x), fqd_from_fq(P.y), fqd_const(FQD_ONE)};
+  const g1jd jac{fqd_from_fq(fq_mul(P.x, z2)), fqd_from_fq(fq_mul(P.y, fq_mul(z2, z))), fqd_from_fq(z)};
+  g1jd T[G1D_TABS], TS[G1D_TAB_N], TD[G1D_TAB_N];
+  for (int v = 0; v < 4; v++) {  // affine source, Jacobian source, table of S apart, both tables apart
+    g1d_build_tables(v == 1 ? jac : aff, T, v < 2 ? 3 : v == 2 ? 2 : 4);
+    if (v >= 2) g1d_table15(aff, TS);
+    if (v == 3) g1d_table15_ni(T[0], TD);
+    const g1jd* ts = v >= 2 ? TS : T + G1D_TAB_N;
+    const g1jd* td = v == 3 ? TD : T;
+    if (!same(want, g1d_mul_u128_tab(ts, td, k4, false))) return 0;
+    if (!same(want_phi, g1d_mul_u128_tab(ts, td, k4, true))) return 0;
+  }
+  return 1;
+}
 // g2d_add (digit tower, exact special cases) against g2_add over the cases the combine's lane tree
 // can meet: P + Q, P + P, P + (-P), O + P, P + O, O + O, with the operands' Z scaled by z0
 // (Jacobian inputs, not only Z = 1).  Returns a bit mask of the cases that agree (63 = all).
