@@ -581,6 +581,101 @@ HBX_HD fq12d fq12d_mul_by_01v(const fq12d& f, const fq2d& c0, const fq2d& c1) {
   return fq12d{fq6d_reduce(fq6d_add(fq6d_mul_v(bv), aa)), fq6d_reduce(fq6d_sub(fq6d_sub(s, aa), bv))};
 }
 
+// x * s with s1 - s0 given (ds): fq2d_mul whose multiplier's difference vector is formed by the
+// caller, once for several products by the same s.  Operand bounds as fq2d_mul.
+HBX_HD fq2d fq2d_mul_ds(const fq2d& x, const fq2d& s, const int32_t (&ds)[14]) {
+  HBX_DBOUND(x.c0, 2 * DN); HBX_DBOUND(x.c1, 2 * DN); HBX_DBOUND(s.c0, 2 * DN); HBX_DBOUND(s.c1, 2 * DN);
+  HBX_COUNT_FQMUL(); HBX_COUNT_FQMUL(); HBX_COUNT_FQMUL();
+  int32_t dx[14];
+#pragma unroll
+  for (int i = 0; i < 14; i++) dx[i] = x.c0.d[i] - x.c1.d[i];
+  fq2d r;
+  fqd_redc2(
+      [&](int k, int jlo, int jhi, int64_t& X, int64_t& Y) {
+        int64_t t0 = 0, t1 = 0, t2 = 0;
+#pragma unroll
+        for (int j = jlo; j <= jhi; j++) {
+          t0 += (int64_t)x.c0.d[j] * (int64_t)s.c0.d[k - j];
+          t1 += (int64_t)x.c1.d[j] * (int64_t)s.c1.d[k - j];
+          t2 += (int64_t)dx[j] * (int64_t)ds[k - j];
+        }
+        X = t0 - t1;
+        Y = t2 + t0 + t1;
+      },
+      r.c0, r.c1);
+  return r;
+}
+// a * s, s in Fq2 (an Fq6 times an Fq2 scalar): three Fq2 products with one multiplier, whose
+// Karatsuba difference vector s1 - s0 is formed once; out0 / out1 / out2 take a0 s, a1 s, a2 s as
+// they come (a fence after each product, as pairingd.hpp fq6d_mul_acc1: one product's temporaries
+// are dead before the next starts).  a0, a1, a2, s: sums of at most two normalised values.
+template <class Out0, class Out1, class Out2>
+HBX_HD void fq6d_mul_fq2_each(const fq2d& a0, const fq2d& a1, const fq2d& a2, const fq2d& s, Out0 out0, Out1 out1,
+                              Out2 out2) {
+  int32_t ds[14];
+#pragma unroll
+  for (int i = 0; i < 14; i++) ds[i] = s.c1.d[i] - s.c0.d[i];
+  out0(fq2d_mul_ds(a0, s, ds));
+  HBX_SEQ();
+  out1(fq2d_mul_ds(a1, s, ds));
+  HBX_SEQ();
+  out2(fq2d_mul_ds(a2, s, ds));
+  HBX_SEQ();
+}
+
+// f * (1 + beta v + alpha v w): a line scaled to constant term 1 (an Fq2 factor, which the final
+// exponentiation's easy part maps to 1).  With f = f0 + f1 w and w^2 = v,
+//   f l = f + v g,   g = f (beta + alpha w) = (P + v Q) + (R - P - Q) w,
+//   P = f0 beta,  Q = f1 alpha,  R = (f0 + f1)(alpha + beta),
+// each an Fq6 times an Fq2 scalar: nine Fq2 products (fq12d_mul_by_01v: ten); the products by v
+// are coefficient shifts.  f reduced or conjugated reduced, alpha and beta normalised; the operand
+// sums f0 + f1 and alpha + beta enter their products as they are (two normalised values).  Every
+// product is folded into the result at once: a digit of c0 sums at most 5 normalised values, one
+// of c1 at most 7 (below 8 x 2^28), and the values (at most 12 products in (-p, 2p) and f) stay
+// far inside fqd_reduce's range.  Reduced on exit.
+HBX_HD fq12d fq12d_mul_by_1ab(const fq12d& f, const fq2d& alpha, const fq2d& beta) {
+  fq6d c0 = f.c0, c1 = f.c1;
+  // v R into c1
+  fq6d_mul_fq2_each(
+      fq2d_add(f.c0.c0, f.c1.c0), fq2d_add(f.c0.c1, f.c1.c1), fq2d_add(f.c0.c2, f.c1.c2), fq2d_add(alpha, beta),
+      [&](const fq2d& t) { c1.c1 = fq2d_add(c1.c1, t); },
+      [&](const fq2d& t) { c1.c2 = fq2d_add(c1.c2, t); },
+      [&](const fq2d& t) { c1.c0 = fq2d_add(c1.c0, fq2d_mul_xi(t)); });
+  // v P into c0, out of c1
+  fq6d_mul_fq2_each(
+      f.c0.c0, f.c0.c1, f.c0.c2, beta,
+      [&](const fq2d& t) {
+        c0.c1 = fq2d_add(c0.c1, t);
+        c1.c1 = fq2d_sub(c1.c1, t);
+      },
+      [&](const fq2d& t) {
+        c0.c2 = fq2d_add(c0.c2, t);
+        c1.c2 = fq2d_sub(c1.c2, t);
+      },
+      [&](const fq2d& t) {
+        const fq2d x = fq2d_mul_xi(t);
+        c0.c0 = fq2d_add(c0.c0, x);
+        c1.c0 = fq2d_sub(c1.c0, x);
+      });
+  // v^2 Q into c0, v Q out of c1
+  fq6d_mul_fq2_each(
+      f.c1.c0, f.c1.c1, f.c1.c2, alpha,
+      [&](const fq2d& t) {
+        c0.c2 = fq2d_add(c0.c2, t);
+        c1.c1 = fq2d_sub(c1.c1, t);
+      },
+      [&](const fq2d& t) {
+        c0.c0 = fq2d_add(c0.c0, fq2d_mul_xi(t));
+        c1.c2 = fq2d_sub(c1.c2, t);
+      },
+      [&](const fq2d& t) {
+        const fq2d x = fq2d_mul_xi(t);
+        c0.c1 = fq2d_add(c0.c1, x);
+        c1.c0 = fq2d_sub(c1.c0, x);
+      });
+  return fq12d{fq6d_reduce(c0), fq6d_reduce(c1)};
+}
+
 // Granger-Scott cyclotomic squaring (field.hpp fq12_cyclotomic_sqr_t)
 HBX_HD void fq4d_sqr(const fq2d& a, const fq2d& b, fq2d& c0, fq2d& c1) {
   const fq2d t0 = fq2d_sqr(a);

@@ -79,6 +79,9 @@ struct hbx_ctx {
   // epoch state
   uint32_t p_ct = 0;
   dbuf U, G2pts, Hj, lines, lines_d, scratch, ct_ok, ct_valid, dec_st;
+  // the one-lane Miller kernel's lines, divided by their constant term (k_normalise_lines), and
+  // the per-proposer flag of a line that has no such form
+  dbuf lines_u, line_degen;
   // own-share mode (hbx_set_own_share): this node's index and secret share (8 LE limbs), and its
   // own decryption shares of the prepared ciphertexts
   uint32_t own_me = UINT32_MAX;
@@ -95,6 +98,7 @@ struct hbx_ctx {
   dbuf S, S_status, fallback, valid, shares_own, present_own, gslot;
   dbuf fe1slot;  // one-lane checks: the final exponentiation's global slots F, T, G (fe1d.hpp)
   uint32_t force_fallback = 0;  // hbx_debug_force_fallback (tests only)
+  uint32_t force_degen = 0;  // hbx_debug_force_degenerate (tests only)
   // the combine's window tables (g1d.hpp; built by k_prepare_lines in the fused epoch call only):
   // cap + 1 slots of G1D_TABS entries per proposer and their presence flags.  They belong to the
   // shares decoded by the last fused prepare (tab_ready; dropped wherever n_shares is reset and
@@ -648,7 +652,7 @@ int hbx_ctx_destroy(hbx_ctx* c) {
                   &c->coin_blob, &c->coin_off,  &c->coin_H, &c->coin_Hp,      &c->coin_lines, &c->coin_scratch, &c->coin_sk,
                   &c->coin_sig96, &c->coin_sig, &c->coin_sig_st, &c->coin_present, &c->coin_valid, &c->coin_comb,
                   &c->coin_comb_st, &c->coin_mpk_comp, &c->coin_mpk, &c->coin_mpk_st, &c->coin_ok, &c->coin_par,
-                  &c->coin_out96, &c->dec_st, &c->own_sk, &c->own_S, &c->own_part, &c->lines_d,
+                  &c->coin_out96, &c->dec_st, &c->own_sk, &c->own_S, &c->own_part, &c->lines_d, &c->lines_u, &c->line_degen,
                   &c->vs_pk, &c->vs_lines_d, &c->coin_lines_d, &c->vs_blob, &c->vs_off, &c->vs_H, &c->vs_lines, &c->vs_scratch, &c->vs_sig96,
                   &c->vs_sig, &c->vs_sig_st, &c->vs_status, &c->fe1slot, &c->fb_lanes, &c->fb_coin, &c->fb_ct, &c->fb_sigs, &c->vk_pk48, &c->vk_pk, &c->vk_pkst, &c->vk_idx, &c->vk_gslot, &c->vk_sk, &c->hs[0], &c->hs[1], &c->hs[2], &c->hs[3], &c->hs[4], &c->hs[5], &c->coin_use, &c->bv_commit48, &c->bv_C, &c->bv_cst, &c->bv_rows,
                   &c->bv_rows48, &c->bv_pst, &c->bv_ackp, &c->bv_acky, &c->bv_vals, &c->bv_out,
@@ -699,6 +703,12 @@ int hbx_get_ct_check_used(const hbx_ctx* c) { return c ? c->ct_check_used : -1; 
 int hbx_debug_force_fallback(hbx_ctx* c, uint32_t every) {
   if (!c) return HBX_E_INVALID_ARG;
   c->force_fallback = every;
+  return HBX_OK;
+}
+
+int hbx_debug_force_degenerate(hbx_ctx* c, uint32_t every) {
+  if (!c) return HBX_E_INVALID_ARG;
+  c->force_degen = every;
   return HBX_OK;
 }
 
@@ -934,6 +944,7 @@ static int prepare_impl(hbx_ctx* c, const uint8_t* d_u_comp, const uint8_t* d_v_
   stream_scope ss_{c, s};
   if (!c->U.ensure((size_t)p * sizeof(g1a)) || !c->G2pts.ensure((size_t)2 * p * sizeof(g2a)) || !c->Hj.ensure((size_t)p * sizeof(g2j)) ||
       !c->lines.ensure((size_t)p * sizeof(line_block)) || !c->lines_d.ensure((size_t)p * sizeof(line_block_d)) ||
+      !c->lines_u.ensure((size_t)p * sizeof(line_block_d)) || !c->line_degen.ensure(p) ||
       !c->scratch.ensure((size_t)2 * p * MILLER_LINES * sizeof(fq2d)) || !c->ct_ok.ensure(p) ||
       !c->ct_valid.ensure(p) || !c->dec_st.ensure((size_t)2 * p * 4))
     return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_prepare_ciphertexts_d: out of device memory");
@@ -980,9 +991,10 @@ static int prepare_impl(hbx_ctx* c, const uint8_t* d_u_comp, const uint8_t* d_v_
                        tab_cap ? c->comb_tab.as<g1jd>() : nullptr, c->comb_tab_ok.as<uint8_t>(), tab_cap, form);
     HIPCHK(c, hipGetLastError());
     const uint32_t nl = 2 * p * MILLER_LINES;
+    HIPCHK(c, hipMemsetAsync(c->line_degen.p, 0, p, s));
     hipLaunchKernelGGL(k_normalise_lines, dim3((nl + 63) / 64), b64, 0, s, c->lines.as<line_pre>(),
                        c->scratch.as<fq2d>(), nl, c->lines_d.as<line_pre_d>(), c->G2pts.as<g2a>(),
-                       c->Hj.as<g2j>());
+                       c->Hj.as<g2j>(), c->lines_u.as<line_pre_d>(), c->line_degen.as<uint8_t>());
   }
   HIPCHK(c, hipGetLastError());
   c->p_ct = p;
@@ -1151,13 +1163,15 @@ static int verify_impl(hbx_ctx* c, const uint8_t* d_shares, const uint8_t* d_pre
       c->fb_last = &c->fb_lanes;
       hipLaunchKernelGGL(k_verify_shares_ml, grid, dim3(64), 0, s, c->S.as<g1a>(), c->S_status.as<int32_t>(),
                          d_present, c->pk_m.as<g1a>(), c->n_keys, c->G2pts.as<g2a>(), c->lines_d.as<line_block_d>(),
-                         ctok, n, c->valid.as<uint8_t>(), me, gs);
+                         ctok, n, c->valid.as<uint8_t>(), me, gs, c->lines_u.as<line_block_d>(),
+                         c->line_degen.as<uint8_t>(), c->force_degen);
       uint8_t* vd = c->valid.as<uint8_t>();
       hipLaunchKernelGGL(k_fe1<0>, grid, dim3(64), 0, s, gs, n, vd, ctok, me, ctv, c->force_fallback);
       hipLaunchKernelGGL(k_fe1<1>, grid, dim3(64), 0, s, gs, n, vd, ctok, me, ctv, c->force_fallback);  // F1 + F2
       hipLaunchKernelGGL(k_fe1<3>, grid, dim3(64), 0, s, gs, n, vd, ctok, me, ctv, c->force_fallback);  // F3 + F4
       hipLaunchKernelGGL(k_fe1<5>, grid, dim3(64), 0, s, gs, n, vd, ctok, me, ctv, c->force_fallback);  // F5 + F6
-      // lanes whose compressed squarings met g3 = 0 (never expected): the single-kernel check
+      // lanes whose compressed squarings met g3 = 0, and the lanes of a proposer with a line whose
+      // constant term is 0 (neither ever expected): the single-kernel check
       hipLaunchKernelGGL(k_verify_shares, grid, dim3(64), 0, s, c->S.as<g1a>(), c->S_status.as<int32_t>(), d_present,
                          c->pk_m.as<g1a>(), c->n_keys, c->G2pts.as<g2a>(), c->lines_d.as<line_block_d>(), ctok, n, vd,
                          me, ctv, 1u, c->fb_lanes.as<uint32_t>());
@@ -2038,7 +2052,7 @@ static int verify_sig_impl(hbx_ctx* c, const uint8_t* d_sig96, const uint8_t* d_
     HIPCHK(c, hipGetLastError());
     const uint32_t nl = count * MILLER_LINES;
     hipLaunchKernelGGL(k_normalise_lines, dim3((nl + 63) / 64), dim3(64), 0, s, c->coin_lines.as<line_pre>(),
-                       c->coin_scratch.as<fq2d>(), nl, c->coin_lines_d.as<line_pre_d>(), nullptr, nullptr);
+                       c->coin_scratch.as<fq2d>(), nl, c->coin_lines_d.as<line_pre_d>(), nullptr, nullptr, nullptr, nullptr);
     HIPCHK(c, hipGetLastError());
     c->coin_lines_ready = true;
     // the lines are built on this call's stream: move the prepare event past them, so a later
@@ -2167,7 +2181,7 @@ int hbx_verify_sigs(hbx_ctx* c, const uint8_t* pk48, const uint8_t* msg_blob, co
   HIPCHK(c, hipGetLastError());
   const uint32_t nl = count * MILLER_LINES;
   hipLaunchKernelGGL(k_normalise_lines, dim3((nl + 63) / 64), dim3(64), 0, s, c->vs_lines.as<line_pre>(),
-                     c->vs_scratch.as<fq2d>(), nl, c->vs_lines_d.as<line_pre_d>(), nullptr, nullptr);
+                     c->vs_scratch.as<fq2d>(), nl, c->vs_lines_d.as<line_pre_d>(), nullptr, nullptr, nullptr, nullptr);
   HIPCHK(c, hipGetLastError());
   {
     timed t_(c, HBX_K_VERIFY_SIG, s);

@@ -61,7 +61,9 @@ __device__ __forceinline__ uint8_t share_precheck(int32_t dec_status, bool prese
 }
 
 #ifndef HBX_ML_SCALED
-#define HBX_ML_SCALED 1  // the one-lane Miller kernel over lines divided by y_P (pairingd.hpp)
+// the one-lane Miller kernel's line form (pairingd.hpp): 0 the prepared lines as they are, 1 divided
+// by y_P (miller_loop2_scaled_d), 2 divided by their constant term (miller_loop2_unit_d)
+#define HBX_ML_SCALED 2
 #endif
 
 // Internal status of a share whose pairing check waits for its final exponentiation
@@ -340,10 +342,16 @@ template __global__ void k_prepare_lines<false>(g2a*, uint32_t, line_pre_d*, fq2
 // 68 T steps only, and this launch is 68x wider and one inversion deep.
 // The raw lines come in digit form (k_prepare_lines: (c0, c1) in lines_d, c2 in `c2`); the
 // normalised lines go out in both forms, lines_d overwritten in place.
+// With `lines_u` (the decryption checks' lines) each line also goes out divided by its constant
+// term, (c2 / c0, c1 / c0) in digit form (pairingd.hpp miller_loop2_unit_d), off the same
+// inversion; a finite point with a line whose c0 is 0 has no such form and sets degen[proposer]
+// (cleared by the host before the launch): k_verify_shares_ml leaves its checks to the fallback.
 __global__ void __launch_bounds__(64) k_normalise_lines(line_pre* __restrict__ lines,
                                                         const fq2d* __restrict__ c2, uint32_t count,
                                                         line_pre_d* __restrict__ lines_d,
-                                                        const g2a* __restrict__ pts, const g2j* __restrict__ Hj) {
+                                                        const g2a* __restrict__ pts, const g2j* __restrict__ Hj,
+                                                        line_pre_d* __restrict__ lines_u,
+                                                        uint8_t* __restrict__ degen) {
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= count) return;
   const line_pre_d rd = lines_d[k];
@@ -353,7 +361,13 @@ __global__ void __launch_bounds__(64) k_normalise_lines(line_pre* __restrict__ l
   // identity; z = 1 otherwise (one code path for the wave: a branch would run both inversions)
   fq2 z = fq2_one();
   if (Hj && (pt & 1) == 0 && !pts[pt].inf) z = Hj[pt >> 1].z;
-  g2_normalise_line_z(l, fq2d_to_fq2(c2[k]), z);
+  if (lines_u) {
+    line_pre u;
+    if (g2_normalise_line_z2(l, fq2d_to_fq2(c2[k]), z, u) && !pts[pt].inf) degen[pt >> 1] = 1;
+    lines_u[k] = line_to_d(u);
+  } else {
+    g2_normalise_line_z(l, fq2d_to_fq2(c2[k]), z);
+  }
   lines[k] = l;
   lines_d[k] = line_to_d(l);
 }
@@ -424,7 +438,9 @@ __global__ void __launch_bounds__(64) k_verify_shares_ml(const g1a* __restrict__
                                                          const line_block_d* __restrict__ lines,
                                                          const uint8_t* __restrict__ ct_ok, uint32_t n,
                                                          uint8_t* __restrict__ valid, uint32_t me,
-                                                         uint32_t* __restrict__ gslot) {
+                                                         uint32_t* __restrict__ gslot,
+                                                         const line_block_d* __restrict__ lines_u,
+                                                         const uint8_t* __restrict__ degen, uint32_t force_degen) {
   __shared__ uint32_t park[LDS_FQ12D_DWORDS * LDS_FQ12_STRIDE];  // the G1 points, one slot per lane
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t j = blockIdx.y;
@@ -432,13 +448,27 @@ __global__ void __launch_bounds__(64) k_verify_shares_ml(const g1a* __restrict__
   const size_t idx = (size_t)j * n + i;
   uint8_t res = share_precheck(s_status[idx], present == nullptr || present[idx] || i == me, i < n_keys,
                                ct_ok[j] != 0);
+#if HBX_ML_SCALED == 2
+  // a proposer with a line whose constant term is 0 (k_normalise_lines; never expected) has no
+  // form in lines_u: its checks go to the single-kernel check over `lines`, as a degenerate
+  // compressed squaring's do.  force_degen (tests only, hbx_debug_force_degenerate): every
+  // force_degen-th proposer is taken for one.
+  if (res == HBX_SHARE_VALID && (degen[j] || (force_degen && (j % force_degen) == 0))) res = SHARE_FALLBACK;
+#endif
   if (res == HBX_SHARE_VALID) {
     const g1a sh = S[idx], pki = pk[i];
     const bool skipA = sh.inf || G2pts[2 * j].inf;
     const bool skipB = pki.inf || G2pts[2 * j + 1].inf;
     if (!(skipA && skipB)) {
       lds_u32* slot = (lds_u32*)(park + threadIdx.x);
-#if HBX_ML_SCALED
+#if HBX_ML_SCALED == 2
+      // lines divided by their constant term (pairingd.hpp miller_loop2_unit_d): S and -[m] pk_i as they are
+      park_put_fqd(slot, 0, fqd_from_fq(sh.x));
+      park_put_fqd(slot, 1, fqd_from_fq(sh.y));
+      park_put_fqd(slot, 2, fqd_from_fq(pki.x));
+      park_put_fqd(slot, 3, fqd_neg(fqd_from_fq(pki.y)));
+      const fq12d fd = miller_loop2_unit_d(lines_u[j].h, !skipA, lines_u[j].w, !skipB, slot);
+#elif HBX_ML_SCALED
       // lines divided by y_P (pairingd.hpp miller_loop2_scaled_d): (x/y, 1/y) of S and of -[m] pk_i
       park_scaled_points(slot, sh.x, sh.y, sh.inf, pki.x, fq_neg(pki.y), pki.inf);
       const fq12d fd = miller_loop2_scaled_d(lines[j].h, !skipA, lines[j].w, !skipB, slot);

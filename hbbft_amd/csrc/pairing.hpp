@@ -106,6 +106,27 @@ HBX_HD void g2_normalise_line_z(line_pre& l, const fq2& c2, const fq2& z) {
   l.c1 = fq2_mul(fq2_mul(l.c1, z2), inv);
 }
 
+// g2_normalise_line_z, and the same raw line in a second form: u = (c2 / c0, c1 / c0), the line
+// scaled to constant term 1 (pairingd.hpp miller_loop2_unit_d).  Both inverses come from one
+// inversion of the product (Montgomery's trick).  A line with c0 = 0 has no second form: the
+// return value says so, u is (0, 0), and l comes out as g2_normalise_line_z's all the same (the
+// product takes 1 in c0's place).
+HBX_HD bool g2_normalise_line_z2(line_pre& l, const fq2& c2, const fq2& z, line_pre& u) {
+  const fq2 z2 = fq2_sqr(z);
+  const fq2 d = fq2_mul(c2, fq2_mul(z2, z));  // the y_P coefficient of the line through (X, Y, Z)
+  const bool degenerate = fq2_is_zero(l.c0);
+  const fq2 e = degenerate ? fq2_one() : l.c0;
+  const fq2 inv = fq2_inv(fq2_mul(d, e));
+  const fq2 inv_d = fq2_mul(inv, e);
+  const fq2 inv_e = degenerate ? fq2_zero() : fq2_mul(inv, d);
+  const fq2 c1 = fq2_mul(l.c1, z2);
+  u.c0 = fq2_mul(d, inv_e);
+  u.c1 = fq2_mul(c1, inv_e);
+  l.c0 = fq2_mul(l.c0, inv_d);
+  l.c1 = fq2_mul(c1, inv_d);
+  return degenerate;
+}
+
 // Prepare the 68 normalised lines of Q (affine, not infinity) in one lane (host tools).
 // `scratch` holds 2*68 Fq2 of workspace (raw c2 values and their prefix products for one
 // batched inversion).

@@ -360,6 +360,35 @@ HBX_HD fq12d miller_loop2_scaled_d(const line_pre_d* LA, bool useA, const line_p
   }
   return fq12d_conj(f);
 }
+// miller_loop2_parked_d over lines divided by their constant term (k_normalise_lines' second
+// table: L.c0 = a = c2 / c0, L.c1 = b = c1 / c0 of the raw line c0 + c1 x v + c2 y v w): the slot
+// holds (x_A, y_A, x_B, y_B) as miller_loop2_parked_d's, each line becomes 1 + (b x) v + (a y) v w
+// and its product is fq12d_mul_by_1ab: nine Fq2 products, and no inversion per lane.  The element
+// differs from miller_loop2_parked_d's by a product of Fq2 factors (c2 / c0 per line), which the
+// final exponentiation maps to 1: the same verdict.  A line with c0 = 0 has no such form; the
+// caller takes another loop for a point that has one (k_normalise_lines' flag).
+HBX_HD fq12d miller_loop2_unit_d(const line_pre_d* LA, bool useA, const line_pre_d* LB, bool useB, lds_u32* park) {
+  fq12d f = fq12d_one();
+  int k = 0;
+#pragma unroll 1
+  for (int i = 62; i >= 0; i--) {
+    if (i != 62) f = fq12d_sqr_parked(f, park);
+    const int steps = ((BLS_X >> i) & 1) ? 4 : 2;  // (A, B) lines of the doubling [+ addition]
+#pragma unroll 1
+    for (int s = 0; s < steps; s++) {
+      const bool b = (s & 1) != 0;
+      const line_pre_d L = ld_uniform((b ? LB : LA) + k);
+      if (b ? useB : useA) {
+        HBX_SEQ();
+        const fqd px = park_get_fqd(park, b ? 2 : 0);
+        const fqd py = park_get_fqd(park, b ? 3 : 1);
+        f = fq12d_mul_by_1ab(f, fq2d_mul_fq(L.c0, py), fq2d_mul_fq(L.c1, px));
+      }
+      if (b) k++;
+    }
+  }
+  return fq12d_conj(f);
+}
 // (x / y, 1 / y) of the two affine G1 points into the slot (words 0..3), one Fq inversion for both
 // (Montgomery's trick); a point at infinity contributes 1 (its pair is not used)
 #ifndef HBX_ML_INV

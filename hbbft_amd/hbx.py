@@ -76,6 +76,7 @@ EXPORTS = (
     "hbx_get_verify_lanes_used",
     "hbx_set_combine_lanes",
     "hbx_debug_force_fallback",
+    "hbx_debug_force_degenerate",
     "hbx_get_fallback_lanes",
     "hbx_debug_set_combine_margin",
     "hbx_get_combine_slow_terms",
@@ -228,6 +229,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.hbx_get_verify_lanes_used.argtypes = [P]
     lib.hbx_set_combine_lanes.argtypes = [P, ctypes.c_int]
     lib.hbx_debug_force_fallback.argtypes = [P, u32]
+    lib.hbx_debug_force_degenerate.argtypes = [P, u32]
     lib.hbx_get_fallback_lanes.argtypes = [P]
     lib.hbx_get_fallback_lanes.restype = ctypes.c_int64
     lib.hbx_debug_set_combine_margin.argtypes = [P, ctypes.c_int32]
@@ -369,6 +371,11 @@ class Context:
         """hbx_debug_force_fallback (tests only): route every ``every``-th sender's one-lane check
         through the single-kernel fallback (0 = off)."""
         self._check(self.lib.hbx_debug_force_fallback(self.h, every))
+
+    def debug_force_degenerate(self, every: int):
+        """hbx_debug_force_degenerate (tests only): treat every ``every``-th proposer's lines as having
+        no constant-term-1 form, so its one-lane checks go through the single-kernel fallback (0 = off)."""
+        self._check(self.lib.hbx_debug_force_degenerate(self.h, every))
 
     def fallback_lanes(self) -> int:
         """hbx_get_fallback_lanes: checks of the last launch with a fallback path (one-lane decryption

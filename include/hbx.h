@@ -162,10 +162,19 @@ int hbx_get_verify_lanes_used(const hbx_ctx* ctx);
  * can choose -- a ciphertext with r = 3(x^2 - 1), for which every honest share's check is 1 after
  * the easy part -- is decided by the first step without a fallback.) */
 int hbx_debug_force_fallback(hbx_ctx* ctx, uint32_t every);
+/* Tests only: in one-lane decryption-share checks, treat every `every`-th proposer (0 = none, the
+ * default) as if one of the lines of its H' or W had a zero constant term, which the one-lane Miller
+ * kernel's line form (divided by that term) cannot hold: every checkable share of such a proposer,
+ * and in own-share mode its ciphertext check, is decided by the fallback path (the single-kernel
+ * one-lane check over the lines divided by their y coefficient) and counted by
+ * hbx_get_fallback_lanes.  Results are unchanged.  (A real line has a zero constant term with
+ * probability ~2^-760 per line for a hash output; a proposer who chooses W to hit one only moves
+ * its own column to the slower path.) */
+int hbx_debug_force_degenerate(hbx_ctx* ctx, uint32_t every);
 /* Checks of the last share-check launch (decryption-share, coin, the pair-lane ciphertext checks
  * of hbx_sk_decrypt or the pair-lane signature checks of hbx_verify_sigs_keyed, the latter two
  * summed over that call's chunks -- whichever came last) that the fallback path
- * decided: 0 unless hbx_debug_force_fallback is on, and 0 when that launch used a lane
+ * decided: 0 unless hbx_debug_force_fallback or hbx_debug_force_degenerate is on, and 0 when that launch used a lane
  * count without a fallback path (decryption shares at lanes 2/3/6/7, coin at one lane).  The four
  * kinds count separately; "last" is host call order, so the value is meaningful when the caller
  * reads it after the launch it asks about (waits for the context's streams).  Diagnostics: no

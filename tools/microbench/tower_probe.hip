@@ -90,6 +90,10 @@ PROBE_KERNEL(p_fq12d_sqr) { st_fq12d(out, 0, fq12d_sqr(ld_fq12d(in, 0))); }
 #if PROBE_ON(fq12d_mul_by_01v)
 PROBE_KERNEL(p_fq12d_mul_by_01v) { st_fq12d(out, 0, fq12d_mul_by_01v(ld_fq12d(in, 0), ld_fq2d(in, 12), ld_fq2d(in, 14))); }
 #endif
+#if PROBE_ON(fq12d_mul_by_1ab)
+// the product by a line divided by its constant term (the one-lane Miller kernel's, pairingd.hpp)
+PROBE_KERNEL(p_fq12d_mul_by_1ab) { st_fq12d(out, 0, fq12d_mul_by_1ab(ld_fq12d(in, 0), ld_fq2d(in, 12), ld_fq2d(in, 14))); }
+#endif
 #if PROBE_ON(fq12d_cyclotomic_sqr)
 PROBE_KERNEL(p_fq12d_cyclotomic_sqr) { st_fq12d(out, 0, fq12d_cyclotomic_sqr(ld_fq12d(in, 0))); }
 #endif
