@@ -169,145 +169,23 @@ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
 
 // out rows = XOR_c coef[o][c] * in rows c, byte columns; needs L % 4 == 0 (dword rows).  A wave
 // covers 64 * D consecutive dwords of every row (lane l: dwords l, l + 64, ...) and accumulates
-// CH output rows per pass over the inputs, two inputs per step so the 6 lookups of a step fold
-// into the accumulator with 3 v_bitop3 (4.5 VALU ops per coefficient and data dword).  The
-// pass's tables are staged in LDS ([c][o]: T0/T1 as one 16-byte entry, T2 packed 4 per entry;
-// wave-uniform broadcast reads); outputs past n_out get zero tables and are not stored, inputs
-// are read one step ahead of use.  grid (ceil(L / (4 * 256 * D)), inst), dynamic LDS
-// rs_perm_lds_bytes(k, CH); job_stride as k_rs_code (0: job 0 / tables[0] for all instances).
-__host__ __device__ constexpr size_t rs_perm_lds_bytes(uint32_t k, int ch) {
-  return (size_t)((k + 1) & ~1u) * ch * 20;
-}
-
-#ifndef HBX_RS_LOADS
-#define HBX_RS_LOADS 0  // 1: branch-free clamped loads (r06s: 0.474 vs 0.467 ms on encode, kept off)
-#endif
-#if HBX_IN_TU(6)
-template <int CH, int D>
-__global__ void __launch_bounds__(256) k_rs_code_perm(uint8_t* __restrict__ shards, size_t inst_stride, uint32_t L,
-                                                      uint32_t k, const rs_job* __restrict__ jobs,
-                                                      const gf_ptab* __restrict__ tables, uint32_t job_stride) {
-  static_assert(CH % 4 == 0, "T2 entries are packed four per 16 bytes");
-  extern __shared__ uint4 rs_lds[];
-  const uint32_t kp = (k + 1) & ~1u;
-  uint4* tab01 = rs_lds;                 // [kp][CH]
-  uint4* tab2 = rs_lds + (size_t)kp * CH;  // [kp][CH / 4]
-  const uint32_t inst = blockIdx.y;
-  const rs_job* J = jobs + (size_t)inst * job_stride;
-  const int no = ld_uniform(&J->n_out);
-  if (no == 0) return;
-  const uint32_t Ld = L >> 2;
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t wave0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 64 * D;
-  uint32_t* base = reinterpret_cast<uint32_t*>(shards + (size_t)inst * inst_stride);
-  const gf_ptab* tb = tables + (size_t)inst * job_stride * RS_MAX_N * k;
-  bool ok[D];
-#pragma unroll
-  for (int j = 0; j < D; j++) ok[j] = wave0 + lane + 64 * j < Ld;
-#if HBX_RS_LOADS
-  // Branch-free loads: lanes past the row end read its last dword and inputs past k (the odd
-  // k's pad row) re-read row k - 1 -- their results are not stored / their tables are zero.
-  uint32_t off[D];
-#pragma unroll
-  for (int j = 0; j < D; j++) off[j] = min(wave0 + lane + 64 * j, Ld - 1);
-  auto load_in = [&](uint32_t c, uint32_t* d) {
-    const uint32_t* src = base + (size_t)ld_uniform(&J->in_idx[c < k ? c : k - 1]) * Ld;
-#pragma unroll
-    for (int j = 0; j < D; j++) d[j] = src[off[j]];
-  };
-#else
-  auto load_in = [&](uint32_t c, uint32_t* d) {
-    if (c < k) {
-      const uint32_t* src = base + (size_t)ld_uniform(&J->in_idx[c]) * Ld + wave0 + lane;
-#pragma unroll
-      for (int j = 0; j < D; j++) d[j] = ok[j] ? src[64 * j] : 0u;
-    } else {
-#pragma unroll
-      for (int j = 0; j < D; j++) d[j] = 0u;
-    }
-  };
-#endif
-  // passes of CH outputs spread over grid.z (host: ceil(expected outputs / CH)); more outputs
-  // than the grid covers loop here
-  for (int o0 = blockIdx.z * CH; o0 < no; o0 += gridDim.z * CH) {
-    __syncthreads();  // previous pass done with the tables
-    for (uint32_t e = threadIdx.x; e < kp * CH; e += blockDim.x) {
-      const uint32_t c = e / CH, o = e % CH;
-      gf_ptab t{};
-      if (c < k && o0 + (int)o < no) t = tb[(size_t)(o0 + o) * k + c];
-      tab01[e] = make_uint4(t.w[0], t.w[1], t.w[2], t.w[3]);
-      reinterpret_cast<uint32_t*>(tab2)[e] = t.w[4];
-    }
-    __syncthreads();
-    uint32_t acc[CH][D];
-#pragma unroll
-    for (int o = 0; o < CH; o++)
-#pragma unroll
-      for (int j = 0; j < D; j++) acc[o][j] = 0;
-    uint32_t na[D], nb[D];
-    load_in(0, na);
-    load_in(1, nb);
-#pragma unroll 1
-    for (uint32_t c = 0; c < kp; c += 2) {
-      uint32_t a0[D], a1[D], a2[D], b0[D], b1[D], b2[D];
-#pragma unroll
-      for (int j = 0; j < D; j++) {
-        a0[j] = na[j] & 0x07070707u;
-        a1[j] = (na[j] >> 3) & 0x07070707u;
-        a2[j] = (na[j] >> 6) & 0x03030303u;
-        b0[j] = nb[j] & 0x07070707u;
-        b1[j] = (nb[j] >> 3) & 0x07070707u;
-        b2[j] = (nb[j] >> 6) & 0x03030303u;
-      }
-      load_in(c + 2, na);
-      load_in(c + 3, nb);
-      const uint4* ta = tab01 + (size_t)c * CH;
-      const uint4* tc = tab2 + (size_t)c * (CH / 4);
-#pragma unroll
-      for (int o4 = 0; o4 < CH; o4 += 4) {
-        const uint4 t2a = tc[o4 / 4], t2b = tc[CH / 4 + o4 / 4];
-        const uint32_t t2av[4] = {t2a.x, t2a.y, t2a.z, t2a.w}, t2bv[4] = {t2b.x, t2b.y, t2b.z, t2b.w};
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          const int o = o4 + q;
-          const uint4 A = ta[o], B = ta[CH + o];
-#pragma unroll
-          for (int j = 0; j < D; j++) {
-            uint32_t x = xor3(acc[o][j], __builtin_amdgcn_perm(A.y, A.x, a0[j]), __builtin_amdgcn_perm(A.w, A.z, a1[j]));
-            x = xor3(x, __builtin_amdgcn_perm(0u, t2av[q], a2[j]), __builtin_amdgcn_perm(B.y, B.x, b0[j]));
-            acc[o][j] = xor3(x, __builtin_amdgcn_perm(B.w, B.z, b1[j]), __builtin_amdgcn_perm(0u, t2bv[q], b2[j]));
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int o = 0; o < CH; o++) {
-      if (o0 + o < no) {
-        uint32_t* dst = base + (size_t)ld_uniform(&J->out_idx[o0 + o]) * Ld + wave0 + lane;
-#pragma unroll
-        for (int j = 0; j < D; j++)
-          if (ok[j]) dst[64 * j] = acc[o][j];
-      }
-    }
-  }
-}
-#endif
-
-// The same product over input TRIPLES: a byte's 8 bits split 3 + 3 + 2, and the two 2-bit tops
+// CH output rows per pass over the inputs; outputs past n_out get zero tables and are not
+// stored, inputs are read one step ahead of use.  grid (ceil(L / (4 * 256 * D)), inst, passes),
+// dynamic LDS rs_perm3_lds_bytes(k, CH); job_stride as k_rs_code (0: job 0 / tables[0] for all
+// instances).
+// The inputs are taken in TRIPLES: a byte's 8 bits split 3 + 3 + 2, and the two 2-bit tops
 // of a triple's three inputs (6 bits) are regrouped as two 3-bit lookups into mixed 8-entry
 // tables -- M1[a7 a6 | b6] = c_a (a_top << 6) ^ c_b (b6 << 6), M2[b7 | c7 c6] = c_b (b7 << 7) ^
 // c_c (c_top << 6) -- so a triple costs 8 v_perm + 4 v_bitop3 per output dword: 4.0 VALU ops per
-// coefficient and data dword against the pair kernel's 4.5 (which spends 3 perms on every
-// byte).  LDS per pass: [triple][CH] x 64 B ({T0,T1} of a, b, c; {M1, M2}), staged from the
-// per-coefficient gf_ptab tables; inputs past k (pad of the last triple) have zero tables.
+// coefficient and data dword, against 4.5 when every byte spends its own 3 perms (the pair-wise
+// kernel this one replaced).  LDS per pass: [triple][CH] x 64 B ({T0,T1} of a, b, c; {M1, M2}),
+// staged from the per-coefficient gf_ptab tables (wave-uniform broadcast reads); inputs past k
+// (pad of the last triple) have zero tables.
 __host__ __device__ constexpr size_t rs_perm3_lds_bytes(uint32_t k, int ch) {
   return (size_t)((k + 2) / 3) * ch * 64;
 }
 
 #if HBX_IN_TU(6)
-#ifndef HBX_RS3_WPE
-#define HBX_RS3_WPE 1  // tuning: minimum waves per EU of the triple kernel (__launch_bounds__'s second bound)
-#endif
 // k_rs_code_perm3's coding of one block, with the row pitch apart from the row length: row r is the
 // Ld dwords at base + r * Pd.  The body of the ragged kernel below; the uniform kernel keeps its
 // own copy, because sharing this one moved its register allocation.
@@ -416,7 +294,7 @@ __device__ __forceinline__ void rs_perm3_block(uint32_t* base, uint32_t Ld, uint
 }
 
 template <int CH, int D>
-__global__ void __launch_bounds__(256, HBX_RS3_WPE) k_rs_code_perm3(uint8_t* __restrict__ shards, size_t inst_stride, uint32_t L,
+__global__ void __launch_bounds__(256, 1) k_rs_code_perm3(uint8_t* __restrict__ shards, size_t inst_stride, uint32_t L,
                                                        uint32_t k, const rs_job* __restrict__ jobs,
                                                        const gf_ptab* __restrict__ tables, uint32_t job_stride) {
   extern __shared__ uint4 rs_lds[];
@@ -531,7 +409,7 @@ __global__ void __launch_bounds__(256, HBX_RS3_WPE) k_rs_code_perm3(uint8_t* __r
 // result).  grid (ceil(max row dwords / (256 * D)), inst, passes): the column grid is the
 // largest instance's, and a block past its own instance's row end leaves before it stages tables.
 template <int CH, int D>
-__global__ void __launch_bounds__(256, HBX_RS3_WPE) k_rs_code_perm3_rg(uint8_t* __restrict__ buf,
+__global__ void __launch_bounds__(256, 1) k_rs_code_perm3_rg(uint8_t* __restrict__ buf,
                                                        const rg_desc* __restrict__ desc,
                                                        uint32_t k, const rs_job* __restrict__ jobs,
                                                        const gf_ptab* __restrict__ tables, uint32_t job_stride) {
@@ -545,18 +423,6 @@ __global__ void __launch_bounds__(256, HBX_RS3_WPE) k_rs_code_perm3_rg(uint8_t* 
 #endif
 #if defined(HBX_TU) && HBX_TU == 6
 // the tiles rs_code() (hbx_api.hip) launches, instantiated in this translation unit
-#define HBX_RS_INST(ch, d)                                                                                   \
-  template __global__ void k_rs_code_perm<ch, d>(uint8_t* __restrict__, size_t, uint32_t, uint32_t,            \
-                                                  const rs_job* __restrict__, const gf_ptab* __restrict__, uint32_t);
-HBX_RS_INST(32, 2)
-HBX_RS_INST(32, 4)
-HBX_RS_INST(64, 2)
-HBX_RS_INST(24, 4)
-HBX_RS_INST(48, 2)
-HBX_RS_INST(28, 2)
-HBX_RS_INST(28, 4)
-HBX_RS_INST(44, 2)
-#undef HBX_RS_INST
 #define HBX_RS_INST3(ch, d)                                                                                  \
   template __global__ void k_rs_code_perm3<ch, d>(uint8_t* __restrict__, size_t, uint32_t, uint32_t,           \
                                                    const rs_job* __restrict__, const gf_ptab* __restrict__, uint32_t);

@@ -39,22 +39,11 @@ namespace hbx {
 // word k of this lane at p[k * S] ------------------------------------------------------------------
 constexpr int FE1_WORDS = 156;
 
-// The lane's LDS slot, addressed afresh at every access.  Held as a pointer, the slot address is one
-// more VGPR live across every product; at the steps' register peak the allocator spilled exactly
-// that value and reloaded it from scratch before each operand fetch -- 456 of the 525 scratch
-// reloads of one Fq12 slot product (tools/microbench/fe_probe.hip), each waited on before its
-// ds_read.  Here the lane index comes from v_mbcnt (two VALU ops, no register input) in a volatile
-// asm, so it is recomputed where needed and never held: nothing to spill.
-#if defined(__HIPCC__)
-struct lane_lds {
-  lds_u32* base;  // the block's slot array (wave-uniform); lane l's word k at base[k * 64 + l]
-};
-__device__ __forceinline__ lds_u32* slot_ptr(lane_lds s) {
-  uint32_t l;
-  __asm__ volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return s.base + l;
-}
-#endif
+// The lane's LDS slot is a held pointer.  In the probe of one Fq12 slot product
+// (tools/microbench/fe_probe.hip) that address was the value spilled at the register peak (456 of
+// 525 scratch reloads); a slot addressed afresh at every access (lane index from v_mbcnt, nothing
+// to spill) took the probe 102 -> 91 us, but the step kernels did not move
+// (profiles/r06hi_fe_variants.txt), so the pointer stayed.
 template <class T>
 HBX_HD T* slot_ptr(T* p) {
   return p;
@@ -155,82 +144,8 @@ HBX_HD void s1_copy(PD d_, PS s_) {
 
 // fq6d_zero_ and fq6d_mul_acc1 (acc += a * y, y streamed): pairingd.hpp
 
-// acc_p += a * y and acc_m -= a * y at once (pairingd.hpp fq6d_mul_acc1's Karatsuba, every Fq2
-// product folded into both accumulators): both normalised (or zero) on entry, carry-normalised on exit.
-template <class Y>
-HBX_HD void fq6d_mul_acc_pm(fq6d& acc_p, fq6d& acc_m, const fq6d& a, Y y) {
-  auto fold = [&](int k, const fq2d& t, int sign) __attribute__((always_inline)) {
-    fq2d& p = k == 0 ? acc_p.c0 : k == 1 ? acc_p.c1 : acc_p.c2;
-    fq2d& m = k == 0 ? acc_m.c0 : k == 1 ? acc_m.c1 : acc_m.c2;
-    if (sign > 0) {
-      p = fq2d_add(p, t);
-      m = fq2d_sub(m, t);
-    } else {
-      p = fq2d_sub(p, t);
-      m = fq2d_add(m, t);
-    }
-  };
-  {
-    const fq2d t0 = fq2d_mul(a.c0, y(0));
-    fold(0, t0, 1);
-    fold(1, t0, -1);
-    fold(2, t0, -1);
-  }
-  HBX_SEQ();
-  {
-    const fq2d t1 = fq2d_mul(a.c1, y(1));
-    fold(0, fq2d_mul_xi(t1), -1);
-    fold(1, t1, -1);
-    fold(2, t1, 1);
-  }
-  HBX_SEQ();
-  {
-    const fq2d t2 = fq2d_mul(a.c2, y(2));
-    const fq2d xt2 = fq2d_mul_xi(t2);
-    fold(0, xt2, -1);
-    fold(1, xt2, 1);
-    fold(2, t2, -1);
-  }
-  HBX_SEQ();
-  fold(0, fq2d_mul_xi(fq2d_mul(fq2d_add(a.c1, a.c2), fq2d_add(y(1), y(2)))), 1);
-  HBX_SEQ();
-  fold(1, fq2d_mul(fq2d_add(a.c0, a.c1), fq2d_add(y(0), y(1))), 1);
-  HBX_SEQ();
-  fold(2, fq2d_mul(fq2d_add(a.c0, a.c2), fq2d_add(y(0), y(2))), 1);
-  HBX_SEQ();
-  acc_p = fq6d_norm(acc_p);
-  acc_m = fq6d_norm(acc_m);
-}
-
 // X * Y, X in registers (reduced, or its conjugate), Y the packed value in slot y.  Reduced.
 // Karatsuba over w: c0 = X0 Y0 + v X1 Y1, c1 = (X0 + X1)(Y0 + Y1) - X0 Y0 - X1 Y1.
-#ifndef HBX_FE1_MUL_ORDER
-#define HBX_FE1_MUL_ORDER 0  // 1: the three-Fq6 order below (tools/build_variant.py measures it)
-#endif
-#if HBX_FE1_MUL_ORDER
-// The order keeps at most three Fq6 values beside a product's temporaries (the round-5 order held
-// X, X0 + X1 and three accumulators, ~500 registers): B = X1 Y1 first; X0 + X1 replaces X1; B
-// seeds both outputs (c0 = v B, c1 = -B) and dies; c1 += (X0 + X1)(Y0 + Y1), then X0 Y0 goes into
-// c0 and out of c1 in one pass.  Same element.
-template <int S, class P>
-HBX_HD fq12d fq12d_mul_slot(const fq12d& X, P y) {
-  fq6d c0, c1;
-  fq6d Xs;
-  {
-    fq6d B = fq6d_zero_();
-    fq6d_mul_acc1(B, X.c1, [&](int q) { return s1_get_fq2d<S>(y, 3 + q); });
-    HBX_SEQ();
-    Xs = fq6d_norm(fq6d_add(X.c0, X.c1));
-    c0 = fq6d_norm(fq6d_mul_v(B));
-    c1 = fq6d_neg(B);
-  }
-  HBX_SEQ();
-  fq6d_mul_acc1(c1, Xs, [&](int q) { return fq2d_norm(fq2d_add(s1_get_fq2d<S>(y, q), s1_get_fq2d<S>(y, 3 + q))); });
-  HBX_SEQ();
-  fq6d_mul_acc_pm(c0, c1, X.c0, [&](int q) { return s1_get_fq2d<S>(y, q); });
-  return fq12d{fq6d_reduce(c0), fq6d_reduce(c1)};
-}
-#else
 template <int S, class P>
 HBX_HD fq12d fq12d_mul_slot(const fq12d& X, P y) {
   fq6d A = fq6d_zero_();
@@ -244,40 +159,14 @@ HBX_HD fq12d fq12d_mul_slot(const fq12d& X, P y) {
   fq6d_mul_acc1(C, Xs, [&](int q) { return fq2d_norm(fq2d_add(s1_get_fq2d<S>(y, q), s1_get_fq2d<S>(y, 3 + q))); });
   return fq12d{fq6d_reduce(fq6d_add(A, fq6d_mul_v(B))), fq6d_reduce(fq6d_sub(fq6d_sub(C, A), B))};
 }
-#endif
 
-// Granger-Scott cyclotomic squaring (fieldd.hpp fq12d_cyclotomic_sqr) with a fence after every Fq2
-// squaring: the nine squarings are independent, and unfenced the scheduler interleaves them until
-// the temporaries of all of them are live at once (440 VGPRs spilled around a bare loop of them).
-#ifndef HBX_FE1_CYC_FENCE
-#define HBX_FE1_CYC_FENCE 2  // 2: after every Fq2 squaring, 1: after every Fq4 squaring, 0: none
-#endif
-#if HBX_FE1_CYC_FENCE >= 2
-#define HBX_CYC_SEQ2() HBX_SEQ()
-#else
-#define HBX_CYC_SEQ2() ((void)0)
-#endif
-#if HBX_FE1_CYC_FENCE >= 1
-#define HBX_CYC_SEQ1() HBX_SEQ()
-#else
-#define HBX_CYC_SEQ1() ((void)0)
-#endif
-#ifndef HBX_FE1_LAZY
-#define HBX_FE1_LAZY 1  // 1: Fq4 squarings by fq4d_sqr_lazy (one reduction per output coordinate)
-#endif
+// Granger-Scott cyclotomic squaring (fieldd.hpp fq12d_cyclotomic_sqr), its three Fq4 squarings
+// lazily reduced (fq4d_sqr_lazy: one reduction per output coordinate) with a fence after each: the
+// squarings are independent, and unfenced the scheduler interleaves them until the temporaries of
+// all of them are live at once (440 VGPRs spilled around a bare loop of them).
 HBX_HD void fq4d_sqr_seq(const fq2d& a, const fq2d& b, fq2d& c0, fq2d& c1) {
-#if HBX_FE1_LAZY
   fq4d_sqr_lazy(a, b, c0, c1);
-  HBX_CYC_SEQ1();
-#else
-  const fq2d t0 = fq2d_sqr(a);
-  HBX_CYC_SEQ2();
-  const fq2d t1 = fq2d_sqr(b);
-  HBX_CYC_SEQ2();
-  c0 = fq2d_norm(fq2d_add(fq2d_mul_xi(t1), t0));
-  c1 = fq2d_norm(fq2d_sub(fq2d_sub(fq2d_sqr(fq2d_add(a, b)), t0), t1));
-  HBX_CYC_SEQ1();
-#endif
+  HBX_SEQ();
 }
 HBX_HD fq12d fq12d_cyclotomic_sqr_seq(const fq12d& f) {
   fq2d z0 = f.c0.c0, z4 = f.c0.c1, z3 = f.c0.c2;
@@ -318,7 +207,6 @@ HBX_HD fq2d fq2d_lin(const fq2d& a3, const fq2d& b2, bool minus) {  // reduce(3 
   return fq2d_reduce(minus ? fq2d_sub(a, b) : fq2d_add(a, b));
 }
 HBX_HD void karabina_sqr(fq12c& c) {
-#if HBX_FE1_LAZY
   // (g3 + g2 Y)^2 = (g3^2 + xi g2^2) + 2 g2 g3 Y and (g1 + g5 Y)^2 = (g1^2 + xi g5^2) + 2 g1 g5 Y:
   // the six squarings as two lazily reduced Fq4 squarings (fieldd.hpp fq4d_sqr_lazy)
   fq2d p1, x23, p2, x15;
@@ -331,25 +219,6 @@ HBX_HD void karabina_sqr(fq12c& c) {
   const fq2d n3 = fq2d_lin(fq2d_norm(fq2d_mul_xi(x15)), c.g3, false);
   const fq2d n5 = fq2d_lin(x23, c.g5, false);
   c = fq12c{n1, n2, n3, n5};
-#else
-  const fq2d s1 = fq2d_sqr(c.g1);
-  HBX_SEQ();
-  const fq2d s5 = fq2d_sqr(c.g5);
-  HBX_SEQ();
-  const fq2d x15 = fq2d_norm(fq2d_sub(fq2d_sub(fq2d_sqr(fq2d_add(c.g1, c.g5)), s1), s5));  // 2 g1 g5
-  HBX_SEQ();
-  const fq2d s3 = fq2d_sqr(c.g3);
-  HBX_SEQ();
-  const fq2d s2 = fq2d_sqr(c.g2);
-  HBX_SEQ();
-  const fq2d x23 = fq2d_norm(fq2d_sub(fq2d_sub(fq2d_sqr(fq2d_add(c.g2, c.g3)), s2), s3));  // 2 g2 g3
-  HBX_SEQ();
-  const fq2d n1 = fq2d_lin(fq2d_norm(fq2d_add(s3, fq2d_mul_xi(s2))), c.g1, true);
-  const fq2d n2 = fq2d_lin(fq2d_norm(fq2d_add(s1, fq2d_mul_xi(s5))), c.g2, true);
-  const fq2d n3 = fq2d_lin(fq2d_norm(fq2d_mul_xi(x15)), c.g3, false);
-  const fq2d n5 = fq2d_lin(x23, c.g5, false);
-  c = fq12c{n1, n2, n3, n5};
-#endif
 }
 // decompressed element (reduced); `degenerate` set when g3 = 0
 #ifndef HBX_KARA_INV_CALL

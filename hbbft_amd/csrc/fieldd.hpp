@@ -262,16 +262,6 @@ HBX_HD fqd fqd_sqr(const fqd& a) {
   return r;
 }
 
-// HBX_REDC_FENCE (set per translation unit): a scheduling barrier after every column of the fused
-// Fq2 product loops, so the scheduler cannot hoist later columns' multiply-adds -- at one wave per
-// SIMD it otherwise fills ~190 VGPRs with a single Fq2 product's partial sums, which leaves no
-// room for a live Fq12 (fe1d.hpp).
-#if defined(HBX_REDC_FENCE) && defined(__HIP_DEVICE_COMPILE__)
-#define HBX_COL_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define HBX_COL_FENCE() ((void)0)
-#endif
-
 // Two Montgomery reductions driven by one column loop: (x, y) with x = sum_k X_k 2^(28k),
 // y = sum_k Y_k 2^(28k) given column by column by `col` (X_k, Y_k exact in int64), returns
 // (x / 2^392, y / 2^392) mod p, normalised.
@@ -313,7 +303,6 @@ HBX_HD void fqd_redc2(Col col, fqd& rx, fqd& ry) {
       HBX_LAUNDER(rx.d[k - 14]);
       HBX_LAUNDER(ry.d[k - 14]);
     }
-    HBX_COL_FENCE();
   }
   rx.d[13] = (int32_t)ax;
   ry.d[13] = (int32_t)ay;
@@ -353,7 +342,6 @@ HBX_HD void fqd_redcn(Col col, fqd (&r)[N]) {
         HBX_LAUNDER(r[q].d[k - 14]);
       }
     }
-    HBX_COL_FENCE();
   }
 #pragma unroll
   for (int q = 0; q < N; q++) r[q].d[13] = (int32_t)acc[q];

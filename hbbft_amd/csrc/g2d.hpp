@@ -189,29 +189,14 @@ HBX_HDNI g2jd g2d_add_mixed_nc(const g2jd& T, const fq2d& qx, const fq2d& qy) {
 }
 HBX_HDNI g2jd g2d_add_nc(const g2jd& p, const g2jd& q) { return g2d_add_nc_t(p, q, g2d_one{}); }
 HBX_HDNI g2jd g2d_add(const g2jd& p, const g2jd& q) { return g2d_add_t(p, q, g2d_one{}); }
-#ifndef HBX_G2D_W4_INLINE_DBL
-#define HBX_G2D_W4_INLINE_DBL 1  // 1: the doublings inlined (combine 4.03 -> 3.71 ms), 2: the window additions too (3.70: not worth the code)
-#endif
+// the doublings inlined in the window loop (no call frame: combine 4.03 -> 3.71 ms); the window
+// additions stay calls (inlined too: 3.70 ms, not worth the code)
 HBX_HDNI g2jd g2d_mul_u64_w4(const fq2d& px, const fq2d& py, uint64_t k, bool& inf) {
   return g2d_mul_u64_w4_t(
-      px, py, k, inf,
-      [](const g2jd& a) __attribute__((always_inline)) {
-#if HBX_G2D_W4_INLINE_DBL
-        return g2d_dbl_t(a, g2d_one{});  // the doublings inlined in the window loop: no call frame
-#else
-        return g2d_dbl(a);
-#endif
-      },
-      [](const g2jd& a, const g2jd& b) __attribute__((always_inline)) {
-#if HBX_G2D_W4_INLINE_DBL >= 2
-        return g2d_add_nc_t(a, b, g2d_one{});
-#else
-        return g2d_add_nc(a, b);
-#endif
-      },
+      px, py, k, inf, [](const g2jd& a) __attribute__((always_inline)) { return g2d_dbl_t(a, g2d_one{}); },
+      [](const g2jd& a, const g2jd& b) __attribute__((always_inline)) { return g2d_add_nc(a, b); },
       [](const g2jd& a, const fq2d& x, const fq2d& y) { return g2d_add_mixed_nc(a, x, y); });
 }
-
 
 HBX_HD g2j g2jd_to_g2j(const g2jd& a) { return g2j{fq2d_to_fq2(a.x), fq2d_to_fq2(a.y), fq2d_to_fq2(a.z)}; }
 

@@ -1,9 +1,9 @@
 // G2 arithmetic on a lane GROUP in the signed-digit tower (fieldd.hpp) for the latency-bound
-// chains: hash-to-G2's cofactor clearing (hash.hpp hash_g2_group), as hash.hpp's g2_dbl_group /
-// g2_add_group rounds with 14-digit operands.
+// chains: hash-to-G2's cofactor clearing (hash.hpp hash_g2_group).  The rounds were first written
+// over 12-limb operands; these replaced them.
 //
-// Why (tools/microbench/dblstamp.hip, profiles/r05m_dblstamp.txt): in one 12-limb group doubling
-// the three Fq products take 30 % of the time and the modular additions, selects and broadcasts
+// Why (profiles/r05m_dblstamp.txt): in one 12-limb group doubling
+// the three Fq products took 30 % of the time and the modular additions, selects and broadcasts
 // between them 70 % -- each 12-limb addition is two dependent carry chains (24 steps) plus a
 // select, and a chain runs on one wave, so every dependent step is paid in full.  Here an addition
 // is one digit-wise VALU level, and the only normalisation is fqd_relax: ONE parallel carry step
@@ -11,7 +11,7 @@
 // carry chain or fqd_reduce's.  No value reduction is needed: every coordinate of a group operation's
 // output is a combination of a few product outputs with small coefficients, so values stay below
 // ~32 p, far inside a product's input range (|a b| < p 2^392).  One doubling: 11.4 -> 6.5 us, the
-// same points after 4,096 doublings (tools/microbench/dbld.hip, profiles/r05n_dbld.txt).
+// same points after 4,096 doublings (profiles/r05n_dbld.txt).
 //
 // "Relaxed" below: digits in (-2^28 - 8, 2^28 + 8), value below 2^386.  Product operands are relaxed
 // values or sums of two; anything larger is relaxed first.  The special cases of an addition
@@ -101,8 +101,12 @@ __device__ __forceinline__ fq2d rows_mul(const fqd& r) {
   return fq2d{fqd_sub(fqd_from_row<K>(r), fqd_from_row<K + 1>(r)), fqd_add(fqd_from_row<K + 2>(r), fqd_from_row<K + 3>(r))};
 }
 
-// 2P on the 8 (or 16) lanes of a group (hash.hpp g2_dbl_group, dbl-2009-l), lane s = gl & 7:
-// three rounds, A = X^2, B = Y^2, Y Z; C = B^2, (X + B)^2, E^2; E (D - X3).  Relaxed in and out.
+// 2P on the 8 (or 16) lanes of a group, all holding the same point (curve.hpp g2_dbl's formulas,
+// dbl-2009-l).  The cofactor clearing is ~200 sequential doublings on one point: a latency chain,
+// run by one lane per proposer while the other lanes of its hash group would idle.  Here the lanes
+// split each doubling's 16 Fq products into rounds of independent products, one per lane,
+// exchanged by row broadcasts; Fq2 products by schoolbook (four Fq products on four lanes).
+// Control flow must be group-uniform.  Lane s = gl & 7: three rounds, A = X^2, B = Y^2, Y Z; C = B^2, (X + B)^2, E^2; E (D - X3).  Relaxed in and out.
 __device__ __forceinline__ g2jd g2d_dbl_group(const g2jd& p, int gl) {
   const int s = gl & 7;
   const fqd x0 = p.x.c0, x1 = p.x.c1, y0 = p.y.c0, y1 = p.y.c1, z0 = p.z.c0, z1 = p.z.c1;
@@ -128,7 +132,8 @@ __device__ __forceinline__ g2jd g2d_dbl_n_group(g2jd p, int n, int gl) {
   return p;
 }
 
-// P + Q on the 16 lanes of a group (hash.hpp g2_add_group, add-2007-bl) in five rounds, the same
+// P + Q on the 16 lanes of a group (curve.hpp g2_add's formulas, add-2007-bl): its 16 Fq2 products
+// (43 Fq products) as five rounds of independent Fq products, one per lane, the same
 // special cases as g2_add by exact tests.  Relaxed in and out.
 __device__ __forceinline__ g2jd g2d_add_group_i(const g2jd& p, const g2jd& q, int gl) {
   if (fq2d_is_zero_mod(p.z)) return q;
@@ -210,7 +215,7 @@ __device__ __noinline__ g2jd g2d_mul_gls_d_group(const g2jd& P, int gl) {
   acc = g2d_add_group(g2d_dbl_n_group(acc, 16, gl), Z, gl);
   return g2d_add_group(g2d_dbl_n_group(acc, 16, gl), W, gl);
 }
-// hash.hpp g2_clear_cofactor_group in the digit tower; full = false stops at Q = h_eff P
+// curve.hpp g2_clear_cofactor on the group; full = false stops at Q = h_eff P
 __device__ __noinline__ g2jd g2d_clear_cofactor_group(const g2jd& P, int gl, bool full) {
   const g2jd t1 = g2d_neg(g2d_mul_u64_group(P, BLS_X, gl));
   g2jd t2 = g2d_psi(P);

@@ -327,249 +327,13 @@ HBX_HDNI g2j g2_rand_from_rng(chacha_rng& r) {
 }
 
 #if defined(__HIPCC__)
-// ---- group-cooperative G2 doubling for the cofactor clearing --------------------------------
-// The cofactor clearing is ~200 sequential doublings on one point: a latency chain, run by one
-// lane per proposer while the other lanes of its hash group idle.  Here the 8 lanes of the group
-// (all holding the same point) split each doubling's 16 Fq products into three rounds of
-// independent products, one per lane, exchanged through ds_bpermute (__shfl).  Same formulas
-// as g2_dbl (dbl-2009-l); Fq2 products by schoolbook (four Fq products on four lanes), so the
-// coordinates are equal mod p to g2_dbl's.  Control flow must be group-uniform.
+// the winner's coordinates to every lane of its hash group (hash_g2_group below)
 __device__ __forceinline__ fq fq_from_lane(const fq& v, int src) {
   fq r;
 #pragma unroll
   for (int i = 0; i < 12; i++) r.l[i] = (uint32_t)__shfl((int)v.l[i], src, 64);
   return r;
 }
-// Lane K of the calling lane's 16-lane row (= its group: groups here are 16 aligned lanes), to
-// every lane of the row: a DPP row_newbcast move per limb -- VALU, no LDS round trip as with
-// __shfl.  K must be a constant; all 16 lanes of the row must be active.
-template <int K>
-__device__ __forceinline__ fq fq_from_row(const fq& v) {
-  static_assert(K >= 0 && K < 16, "row lane");
-  dpp_guard_src<16, K>();
-  fq r;
-#pragma unroll
-  for (int i = 0; i < 12; i++) r.l[i] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v.l[i], 0x150 + K, 0xf, 0xf, false);
-  return r;
-}
-__device__ __forceinline__ fq fq_sel8(int s, const fq& v0, const fq& v1, const fq& v2, const fq& v3, const fq& v4,
-                                      const fq& v5, const fq& v6, const fq& v7) {
-  fq r;
-#pragma unroll
-  for (int i = 0; i < 12; i++) {
-    const uint32_t lo = (s & 2) ? ((s & 1) ? v3.l[i] : v2.l[i]) : ((s & 1) ? v1.l[i] : v0.l[i]);
-    const uint32_t hi = (s & 2) ? ((s & 1) ? v7.l[i] : v6.l[i]) : ((s & 1) ? v5.l[i] : v4.l[i]);
-    r.l[i] = (s & 4) ? hi : lo;
-  }
-  return r;
-}
-__device__ __forceinline__ fq fq_sel16(int s, const fq (&v)[16]) {
-  fq r;
-#pragma unroll
-  for (int i = 0; i < 12; i++) {
-    uint32_t t = v[0].l[i];
-#pragma unroll
-    for (int k = 1; k < 16; k++) t = (s == k) ? v[k].l[i] : t;
-    r.l[i] = t;
-  }
-  return r;
-}
-
-#ifndef HBX_DBL_MARK
-#define HBX_DBL_MARK(k)  // timing hooks (tools/microbench/dblstamp.hip: clock stamps between the
-#define HBX_DBL_USE(v)   // segments; USE pins a product's result before the next stamp)
-#endif
-__device__ __forceinline__ g2j g2_dbl_group(const g2j& p, int gl, int gbase) {
-  const int s = gl & 7;
-  const fq x0 = p.x.c0, x1 = p.x.c1, y0 = p.y.c0, y1 = p.y.c1, z0 = p.z.c0, z1 = p.z.c1;
-  // round 1: A = X^2 (lanes 0, 1), B = Y^2 (2, 3), Y Z (4..7)
-  HBX_DBL_MARK(0);
-  const fq a1 = fq_sel8(s, fq_add(x0, x1), x0, fq_add(y0, y1), y0, y0, y1, y0, y1);
-  const fq b1 = fq_sel8(s, fq_sub(x0, x1), x1, fq_sub(y0, y1), y1, z0, z1, z1, z0);
-  HBX_DBL_USE(a1);
-  HBX_DBL_USE(b1);
-  HBX_DBL_MARK(1);
-  fq r = fq_mul_inl(a1, b1);
-  HBX_DBL_USE(r);
-  HBX_DBL_MARK(2);
-  const fq2 A = fq2{fq_from_row<0>(r), fq_dbl(fq_from_row<1>(r))};
-  const fq2 B = fq2{fq_from_row<2>(r), fq_dbl(fq_from_row<3>(r))};
-  const fq2 YZ = fq2{fq_sub(fq_from_row<4>(r), fq_from_row<5>(r)),
-                     fq_add(fq_from_row<6>(r), fq_from_row<7>(r))};
-  // round 2: C = B^2 (0, 1), T = (X + B)^2 (2, 3), F = E^2 with E = 3A (4, 5)
-  const fq2 S = fq2_add(p.x, B);
-  const fq2 E = fq2_add(fq2_dbl(A), A);
-  const fq a2 = fq_sel8(s, fq_add(B.c0, B.c1), B.c0, fq_add(S.c0, S.c1), S.c0, fq_add(E.c0, E.c1), E.c0, E.c0, E.c0);
-  const fq b2 = fq_sel8(s, fq_sub(B.c0, B.c1), B.c1, fq_sub(S.c0, S.c1), S.c1, fq_sub(E.c0, E.c1), E.c1, E.c1, E.c1);
-  HBX_DBL_USE(a2);
-  HBX_DBL_USE(b2);
-  HBX_DBL_MARK(3);
-  r = fq_mul_inl(a2, b2);
-  HBX_DBL_USE(r);
-  HBX_DBL_MARK(4);
-  const fq2 C = fq2{fq_from_row<0>(r), fq_dbl(fq_from_row<1>(r))};
-  const fq2 T = fq2{fq_from_row<2>(r), fq_dbl(fq_from_row<3>(r))};
-  const fq2 F = fq2{fq_from_row<4>(r), fq_dbl(fq_from_row<5>(r))};
-  const fq2 D = fq2_dbl(fq2_sub(fq2_sub(T, A), C));
-  const fq2 X3 = fq2_sub(F, fq2_dbl(D));
-  // round 3: E (D - X3) (0..3)
-  const fq2 G = fq2_sub(D, X3);
-  const fq a3 = fq_sel8(s, E.c0, E.c1, E.c0, E.c1, E.c0, E.c1, E.c0, E.c1);
-  const fq b3 = fq_sel8(s, G.c0, G.c1, G.c1, G.c0, G.c0, G.c1, G.c1, G.c0);
-  HBX_DBL_USE(a3);
-  HBX_DBL_USE(b3);
-  HBX_DBL_MARK(5);
-  r = fq_mul_inl(a3, b3);
-  HBX_DBL_USE(r);
-  HBX_DBL_MARK(6);
-  const fq2 EG = fq2{fq_sub(fq_from_row<0>(r), fq_from_row<1>(r)),
-                     fq_add(fq_from_row<2>(r), fq_from_row<3>(r))};
-  const fq2 C8 = fq2_dbl(fq2_dbl(fq2_dbl(C)));
-  const g2j out{X3, fq2_sub(EG, C8), fq2_dbl(YZ)};
-  HBX_DBL_USE(out.x.c0);
-  HBX_DBL_USE(out.x.c1);
-  HBX_DBL_USE(out.y.c0);
-  HBX_DBL_USE(out.y.c1);
-  HBX_DBL_USE(out.z.c0);
-  HBX_DBL_USE(out.z.c1);
-  HBX_DBL_MARK(7);
-  return out;
-}
-__device__ __forceinline__ g2j g2_dbl_n_group(g2j p, int n, int gl, int gbase) {
-  for (int i = 0; i < n; i++) p = g2_dbl_group(p, gl, gbase);
-  return p;
-}
-// g2_add (add-2007-bl) on 16 lanes of a group holding the same p and q: its 16 Fq2 products
-// (43 Fq products) as five rounds of independent Fq products, one per lane.  Same special cases
-// as g2_add (identities, P = Q, P = -Q), decided group-uniformly.
-struct round16 {
-  fq a[16], b[16];
-};
-__device__ __forceinline__ void r16_mul(round16& R, int k, const fq2& x, const fq2& y) {
-  R.a[k] = x.c0; R.b[k] = y.c0;
-  R.a[k + 1] = x.c1; R.b[k + 1] = y.c1;
-  R.a[k + 2] = x.c0; R.b[k + 2] = y.c1;
-  R.a[k + 3] = x.c1; R.b[k + 3] = y.c0;
-}
-__device__ __forceinline__ void r16_sqr(round16& R, int k, const fq2& x) {
-  R.a[k] = fq_add(x.c0, x.c1); R.b[k] = fq_sub(x.c0, x.c1);
-  R.a[k + 1] = x.c0; R.b[k + 1] = x.c1;
-}
-__device__ __forceinline__ fq r16_run(const round16& R, int gl) { return fq_mul_inl(fq_sel16(gl, R.a), fq_sel16(gl, R.b)); }
-template <int K>
-__device__ __forceinline__ fq2 r16_get_mul(const fq& r) {
-  return fq2{fq_sub(fq_from_row<K>(r), fq_from_row<K + 1>(r)), fq_add(fq_from_row<K + 2>(r), fq_from_row<K + 3>(r))};
-}
-template <int K>
-__device__ __forceinline__ fq2 r16_get_sqr(const fq& r) {
-  return fq2{fq_from_row<K>(r), fq_dbl(fq_from_row<K + 1>(r))};
-}
-__device__ __forceinline__ void r16_clear(round16& R) {
-#pragma unroll
-  for (int i = 0; i < 16; i++) {
-    R.a[i] = fq_zero();
-    R.b[i] = fq_zero();
-  }
-}
-__device__ __noinline__ g2j g2_add_group(const g2j& p, const g2j& q, int gl, int gbase) {
-  if (g2j_is_identity(p)) return q;
-  if (g2j_is_identity(q)) return p;
-  round16 R;
-  r16_clear(R);
-  // round 1: Z1^2, Z2^2, Y1 Z2, Y2 Z1, (Z1 + Z2)^2
-  r16_sqr(R, 0, p.z);
-  r16_sqr(R, 2, q.z);
-  r16_mul(R, 4, p.y, q.z);
-  r16_mul(R, 8, q.y, p.z);
-  r16_sqr(R, 12, fq2_add(p.z, q.z));
-  fq r = r16_run(R, gl);
-  const fq2 Z1Z1 = r16_get_sqr<0>(r), Z2Z2 = r16_get_sqr<2>(r);
-  const fq2 Y1Z2 = r16_get_mul<4>(r), Y2Z1 = r16_get_mul<8>(r);
-  const fq2 ZS = r16_get_sqr<12>(r);
-  // round 2: U1, U2, S1, S2
-  r16_mul(R, 0, p.x, Z2Z2);
-  r16_mul(R, 4, q.x, Z1Z1);
-  r16_mul(R, 8, Y1Z2, Z2Z2);
-  r16_mul(R, 12, Y2Z1, Z1Z1);
-  r = r16_run(R, gl);
-  const fq2 U1 = r16_get_mul<0>(r), U2 = r16_get_mul<4>(r);
-  const fq2 S1 = r16_get_mul<8>(r), S2 = r16_get_mul<12>(r);
-  if (fq2_eq(U1, U2)) {
-    if (fq2_eq(S1, S2)) return g2_dbl_group(p, gl, gbase);
-    return g2_identity();
-  }
-  const fq2 H = fq2_sub(U2, U1);
-  const fq2 rr = fq2_dbl(fq2_sub(S2, S1));
-  // round 3: I = (2H)^2, r^2, Z3 = ((Z1 + Z2)^2 - Z1Z1 - Z2Z2) H
-  r16_sqr(R, 0, fq2_dbl(H));
-  r16_sqr(R, 2, rr);
-  r16_mul(R, 4, fq2_sub(fq2_sub(ZS, Z1Z1), Z2Z2), H);
-  r = r16_run(R, gl);
-  const fq2 I = r16_get_sqr<0>(r), RR = r16_get_sqr<2>(r), Z3 = r16_get_mul<4>(r);
-  // round 4: J = H I, V = U1 I
-  r16_mul(R, 0, H, I);
-  r16_mul(R, 4, U1, I);
-  r = r16_run(R, gl);
-  const fq2 J = r16_get_mul<0>(r), V = r16_get_mul<4>(r);
-  const fq2 X3 = fq2_sub(fq2_sub(RR, J), fq2_dbl(V));
-  // round 5: r (V - X3), S1 J
-  r16_mul(R, 0, rr, fq2_sub(V, X3));
-  r16_mul(R, 4, S1, J);
-  r = r16_run(R, gl);
-  const fq2 Y3 = fq2_sub(r16_get_mul<0>(r), fq2_dbl(r16_get_mul<4>(r)));
-  return g2j{X3, Y3, Z3};
-}
-__device__ __forceinline__ g2j g2_sub_group(const g2j& p, const g2j& q, int gl, int gbase) {
-  return g2_add_group(p, g2_neg(q), gl, gbase);
-}
-
-// g2_mul_u64 / g2_mul_gls_d / g2_clear_cofactor (curve.hpp) with the group doubling and addition
-#define GADD(a, b) g2_add_group(a, b, gl, gbase)
-#define GSUB(a, b) g2_sub_group(a, b, gl, gbase)
-__device__ g2j g2_mul_u64_group(const g2j& p, uint64_t k, int gl, int gbase) {
-  g2j acc = p;
-  const int top = 63 - __builtin_clzll(k);
-  for (int i = top - 1; i >= 0; i--) {
-    acc = g2_dbl_group(acc, gl, gbase);
-    if ((k >> i) & 1) acc = GADD(acc, p);
-  }
-  return acc;
-}
-__device__ g2j g2_mul_gls_d_group(const g2j& P, int gl, int gbase) {
-  const g2j P2 = g2_dbl_group(P, gl, gbase);
-  const g2j P4 = g2_dbl_group(P2, gl, gbase);
-  g2j Z = GADD(P4, P);
-  Z = GADD(g2_dbl_n_group(Z, 4, gl, gbase), Z);
-  Z = GADD(g2_dbl_n_group(Z, 8, gl, gbase), Z);
-  const g2j W = GADD(g2_dbl_group(Z, gl, gbase), P);
-  g2j acc = GADD(g2_dbl_n_group(P2, 3, gl, gbase), P);
-  acc = GADD(g2_dbl_group(acc, gl, gbase), P);
-  acc = g2_dbl_n_group(acc, 1 + 8 + 16, gl, gbase);
-  acc = GADD(acc, Z);
-  acc = GADD(g2_dbl_n_group(acc, 16, gl, gbase), Z);
-  return GADD(g2_dbl_n_group(acc, 16, gl, gbase), W);
-}
-// full = false stops at Q = h_eff P = [3(x^2-1)] h2 P (k_prepare_ct: the checks carry the factor
-// on their G1 side, hbx_api.hip pk_m / G1_MGEN)
-__device__ g2j g2_clear_cofactor_group(const g2j& P, int gl, int gbase, bool full = true) {
-  const g2j t1 = g2_neg(g2_mul_u64_group(P, BLS_X, gl, gbase));
-  g2j t2 = g2_psi(P);
-  g2j t3 = g2_psi(g2_psi(g2_dbl_group(P, gl, gbase)));
-  t3 = GSUB(t3, t2);
-  t2 = GADD(t1, t2);
-  t2 = g2_neg(g2_mul_u64_group(t2, BLS_X, gl, gbase));
-  t3 = GADD(t3, t2);
-  t3 = GSUB(t3, t1);
-  const g2j Q = GSUB(t3, P);
-  if (!full) return Q;
-  const g2j q1 = g2_psi(Q);
-  const g2j q2 = g2_psi(q1);
-  const g2j q3 = g2_psi(q2);
-  const g2j Rp = GSUB(GSUB(GADD(Q, q1), q2), q3);
-  return g2_mul_gls_d_group(Rp, gl, gbase);
-}
-#undef GADD
-#undef GSUB
 
 // hash_g2 by a GROUP of K aligned lanes of one wave (K | 64), same point as g2_rand_from_rng.
 //
@@ -582,9 +346,6 @@ __device__ g2j g2_clear_cofactor_group(const g2j& P, int gl, int gbase, bool ful
 // clearing.  A cleared point equal to the identity makes the sequential loop continue with the next
 // candidate; so does this one (base = winner + 1).  `active` must be group-uniform.
 // Returns true on the lane that holds the result in `out`.
-#ifndef HBX_HASH_GROUPD
-#define HBX_HASH_GROUPD 1  // 1: the cofactor clearing in the digit tower (groupd.hpp), 0: 12-limb rounds
-#endif
 #ifndef HBX_PHASE
 #define HBX_PHASE(k)  // profiling hook (tools/microbench/hashg2.hip records wall-clock stamps)
 #endif
@@ -636,14 +397,10 @@ __device__ bool hash_g2_group(const uint8_t* d32, bool active, g2j& out, bool fu
     const int src = gbase + win;
     const fq2 xw = fq2{fq_from_lane(x.c0, src), fq_from_lane(x.c1, src)};
     const fq2 yw = fq2{fq_from_lane(y.c0, src), fq_from_lane(y.c1, src)};
-#if HBX_HASH_GROUPD
-    {
+    {  // the cooperative cofactor clearing in the digit tower (groupd.hpp)
       const fq2d one{fqd_const(FQD_ONE), fqd_zero()};
       out = g2jd_to_g2j(g2d_clear_cofactor_group(g2jd{fq2d_from_fq2(xw), fq2d_from_fq2(yw), one}, gl, full));
     }
-#else
-    out = g2_clear_cofactor_group(g2j{xw, yw, fq2_one()}, gl, gbase, full);
-#endif
     HBX_PHASE(4);
     const bool ident = g2j_is_identity(out);
     if ((__ballot(ident) & gmask) == 0) return gl == win;

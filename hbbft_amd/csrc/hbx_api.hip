@@ -359,7 +359,7 @@ static const gf_host& gf() {
   return g;
 }
 
-// Byte-permute tables of one coefficient (layout in broadcast.hpp, k_rs_code_perm).
+// Byte-permute tables of one coefficient (layout in broadcast.hpp, gf_ptab).
 static gf_ptab gf_perm_table(uint8_t c) {
   const gf_host& g = gf();
   uint8_t b[20];
@@ -375,44 +375,27 @@ static gf_ptab gf_perm_table(uint8_t c) {
   return t;
 }
 
-// Output rows x dwords per lane of the byte-permute kernel; HBX_RS_TILE (0..7) pins one of the
-// compiled variants for tuning, -1 (unset) picks by output count (rs_auto_tile).
-static int rs_tile() {
-  static const int t = [] {
-    const char* e = getenv("HBX_RS_TILE");
-    return e ? atoi(e) : -1;
-  }();
-  return t;
-}
-
-// HBX_RS_K3=0 keeps the pair kernel (k_rs_code_perm) where the triple one would run.
-static bool rs_k3() {
-  static const bool t = [] {
-    const char* e = getenv("HBX_RS_K3");
-    return !e || atoi(e) != 0;
-  }();
-  return t;
-}
-
-static const int rs_tile_ch[] = {32, 32, 64, 24, 48, 28, 28, 44};
+// The compiled triple tiles (output rows per pass, two dwords per lane), in the order of preference.
+static const int rs_ch3[] = {21, 14, 12, 28, 42};
+static_assert(rs_perm3_lds_bytes(RS_MAX_K, 12) <= 65536, "the 12-row tile's tables fit the LDS for every k");
 
 // The tile whose row count wastes the fewest computed rows on `no` outputs per instance (each
-// pass over the k input rows yields CH outputs; a short last pass still reads all k rows), ties
-// to the larger tile.  r06q_rs_tiles: m = 84 parity rows run 740 GB/s on 32-row tiles (96 rows
-// computed) and 810 GB/s on 28-row ones (84).
-static int rs_auto_tile(uint32_t k, uint32_t no) {
-  static const int cand[] = {2, 4, 7, 0, 5, 3};  // 64, 48, 44, 32, 28, 24 rows, two dwords per lane but 24
-  int best = 3, best_rows = 1 << 30;
-  for (int t : cand) {
-    const int ch = rs_tile_ch[t];
-    if (rs_perm_lds_bytes(k, ch) > 65536) continue;
-    const int rows = (int)((no + ch - 1) / ch) * ch;
-    if (rows < best_rows) best = t, best_rows = rows;
+// pass over the k input rows yields CH outputs; a short last pass still reads all k rows), among
+// those whose tables fit the LDS at this k; ties to the earlier entry: the 21-row tile runs 88
+// VGPRs (5 waves per SIMD) against 105 for 28 rows and 130 for 42 (r06t21: encode 0.405 ->
+// 0.387-0.398 ms, the decode with spread erasures 1.33 -> 1.22 ms)
+static int rs_tile3(uint32_t k, uint32_t no) {
+  int ch = 12, best_rows = 1 << 30;
+  for (int t : rs_ch3) {
+    if (rs_perm3_lds_bytes(k, t) > 65536) continue;
+    const int rows = (int)((no + t - 1) / t) * t;
+    if (rows < best_rows) ch = t, best_rows = rows;
   }
-  return best;
+  return ch;
 }
 
-// One coding pass: the byte-permute kernel when rows are whole dwords, else the LDS log/exp one.
+// One coding pass: the triple byte-permute kernel (4.0 VALU ops per coefficient-dword) when rows
+// are whole dwords, else the LDS log/exp one.
 // `no` is the outputs one instance's pass is expected to write: m on encode; on a reconstruct pass
 // the f = m / 2 erasures of hbbft's fault bound (the bench's pattern; up to m still runs, in more passes).
 static void rs_code(hbx_ctx* c, uint8_t* d_shards, size_t stride, uint32_t L, uint32_t k, uint32_t inst,
@@ -420,64 +403,34 @@ static void rs_code(hbx_ctx* c, uint8_t* d_shards, size_t stride, uint32_t L, ui
                     hipStream_t s) {
   timed t_(c, HBX_K_RS_CODE, s);
   if (no == 0) no = 1;  // grid.z >= 1; the kernels read the true count from the job
-  if (L % 4 == 0 && rs_k3() && rs_tile() < 0) {
-    // triple kernel (4.0 VALU ops per coefficient-dword): tile by output count as below
-    const uint32_t Ld = L / 4;
-    // fewest computed rows, ties to the earlier entry: the 21-row tile runs 88 VGPRs (5 waves per
-    // SIMD) against 105 for 28 rows and 130 for 42 (r06t21: encode 0.405 -> 0.387-0.398 ms, the
-    // decode with spread erasures 1.33 -> 1.22 ms)
-    static const int ch3[] = {21, 14, 12, 28, 42};
-    int ch = 0, best_rows = 1 << 30;
-    for (int t : ch3) {
-      if (rs_perm3_lds_bytes(k, t) > 65536) continue;
-      const int rows = (int)((no + t - 1) / t) * t;
-      if (rows < best_rows) ch = t, best_rows = rows;
-    }
-    static const int pin = [] {
-      const char* e = getenv("HBX_RS_CH3");  // tuning: 100 * D + CH of a compiled triple tile
-      return e ? atoi(e) : 0;
-    }();
-    int d3 = 2;
-    if (pin && rs_perm3_lds_bytes(k, pin % 100) <= 65536) ch = pin % 100, d3 = pin / 100;
-    if (ch) {
-      switch (d3 * 100 + ch) {
-#define HBX_RS_TILE3(c3, d)                                                                                         \
-  hipLaunchKernelGGL((k_rs_code_perm3<c3, d>), dim3((Ld + 256 * d - 1) / (256 * d), inst, (no + c3 - 1) / c3), dim3(256), \
-                     rs_perm3_lds_bytes(k, c3), s, d_shards, stride, L, k, jobs, ptab, job_stride);                  \
-  break;
-        case 242: HBX_RS_TILE3(42, 2)
-        case 228: HBX_RS_TILE3(28, 2)
-        case 214: HBX_RS_TILE3(14, 2)
-        case 212: HBX_RS_TILE3(12, 2)
-        default: HBX_RS_TILE3(21, 2)
-#undef HBX_RS_TILE3
-      }
-      return;
-    }
-  }
-  if (L % 4 == 0) {
-    const uint32_t Ld = L / 4;
-    int tile = rs_tile();
-    if (tile < 0 || tile > 7) tile = rs_auto_tile(k, no);
-    if (rs_perm_lds_bytes(k, rs_tile_ch[tile]) > 65536) tile = 3;  // 24 x 128 x 20 B fits any k
-    switch (tile) {
-#define HBX_RS_TILE(ch, d)                                                                                        \
-  hipLaunchKernelGGL((k_rs_code_perm<ch, d>), dim3((Ld + 256 * d - 1) / (256 * d), inst, (no + ch - 1) / ch), dim3(256), \
-                     rs_perm_lds_bytes(k, ch), s, d_shards, stride, L, k, jobs, ptab, job_stride);                 \
-  break;
-      case 1: HBX_RS_TILE(32, 4)
-      case 2: HBX_RS_TILE(64, 2)
-      case 3: HBX_RS_TILE(24, 4)
-      case 4: HBX_RS_TILE(48, 2)
-      case 5: HBX_RS_TILE(28, 2)
-      case 6: HBX_RS_TILE(28, 4)
-      case 7: HBX_RS_TILE(44, 2)
-      default: HBX_RS_TILE(32, 2)
-#undef HBX_RS_TILE
-    }
-  } else {
+  if (L % 4 != 0) {
     hipLaunchKernelGGL(k_rs_code, dim3((L + 1023) / 1024, inst), dim3(256), 0, s, d_shards, stride, L, k, jobs, coef,
                        job_stride, c->gf_log.as<uint16_t>(), c->gf_exp.as<uint8_t>());
+    return;
+  }
+  const uint32_t Ld = L / 4;
+  int ch = rs_tile3(k, no);
+  // tuning: HBX_RS_CH3 = 200 + CH pins a compiled tile (read once per process); any other value,
+  // or a tile whose tables do not fit the LDS at this k, is ignored
+  static const int pin = [] {
+    const char* e = getenv("HBX_RS_CH3");
+    const int v = e ? atoi(e) - 200 : 0;
+    for (int t : rs_ch3)
+      if (v == t) return v;
+    return 0;
+  }();
+  if (pin && rs_perm3_lds_bytes(k, pin) <= 65536) ch = pin;
+  switch (ch) {
+#define HBX_RS_TILE3(c3)                                                                                          \
+  hipLaunchKernelGGL((k_rs_code_perm3<c3, 2>), dim3((Ld + 511) / 512, inst, (no + c3 - 1) / c3), dim3(256),        \
+                     rs_perm3_lds_bytes(k, c3), s, d_shards, stride, L, k, jobs, ptab, job_stride);                \
+  break;
+    case 42: HBX_RS_TILE3(42)
+    case 28: HBX_RS_TILE3(28)
+    case 14: HBX_RS_TILE3(14)
+    case 12: HBX_RS_TILE3(12)
+    default: HBX_RS_TILE3(21)
+#undef HBX_RS_TILE3
   }
 }
 
@@ -1462,21 +1415,13 @@ static void rg_fill(rg_desc* d, const uint64_t* off, const uint32_t* len, const 
 }
 
 // One ragged coding pass: the triple byte-permute kernel, tiled by output count as rs_code tiles it
-// (rows are dword rows by construction, so the LDS log/exp byte kernel has no part here; the
-// 12-row tile's tables fit the LDS for every k <= 128).
+// (rows are dword rows by construction, so the LDS log/exp byte kernel has no part here).
 static void rs_code_rg(hbx_ctx* c, uint8_t* d_buf, const rg_desc* d_desc, uint32_t max_len, uint32_t k, uint32_t inst,
                        const rs_job* jobs, const gf_ptab* ptab, uint32_t job_stride, uint32_t no, hipStream_t s) {
   timed t_(c, HBX_K_RS_CODE, s);
   if (no == 0) no = 1;
   const uint32_t Ld = (max_len + 3) / 4;
-  static const int ch3[] = {21, 14, 12, 28, 42};
-  int ch = 12, best_rows = 1 << 30;
-  for (int t : ch3) {
-    if (rs_perm3_lds_bytes(k, t) > 65536) continue;
-    const int rows = (int)((no + t - 1) / t) * t;
-    if (rows < best_rows) ch = t, best_rows = rows;
-  }
-  switch (ch) {
+  switch (rs_tile3(k, no)) {
 #define HBX_RS_TILE3RG(c3)                                                                                            \
   hipLaunchKernelGGL((k_rs_code_perm3_rg<c3, 2>), dim3((Ld + 511) / 512, inst, (no + c3 - 1) / c3), dim3(256),         \
                      rs_perm3_lds_bytes(k, c3), s, d_buf, d_desc, k, jobs, ptab, job_stride);                          \

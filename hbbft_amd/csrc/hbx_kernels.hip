@@ -60,12 +60,6 @@ __device__ __forceinline__ uint8_t share_precheck(int32_t dec_status, bool prese
   return HBX_SHARE_VALID;
 }
 
-#ifndef HBX_ML_SCALED
-// the one-lane Miller kernel's line form (pairingd.hpp): 0 the prepared lines as they are, 1 divided
-// by y_P (miller_loop2_scaled_d), 2 divided by their constant term (miller_loop2_unit_d)
-#define HBX_ML_SCALED 2
-#endif
-
 // Internal status of a share whose pairing check waits for its final exponentiation
 // (k_verify_shares_ml -> k_fe1<6>); never visible outside a verification call.
 constexpr uint8_t SHARE_PENDING = 0xFE;
@@ -293,7 +287,6 @@ __global__ void __launch_bounds__(64) k_prepare_lines(g2a* __restrict__ pts, uin
   const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t k = gid / LINE_K;
   const int gl = (int)(gid % LINE_K);
-  const int gbase = (int)(threadIdx.x & 63) - gl;
   if (k >= count) return;  // whole groups (LINE_K | 64)
   g2a q = pts[k];
   if (Hj && (k & 1) == 0) {  // (X, Y) of the Jacobian hash point; Z enters in k_normalise_lines
@@ -325,7 +318,6 @@ __global__ void __launch_bounds__(64) k_prepare_lines(g2a* __restrict__ pts, uin
     return;
   }
   // the steps in the digit tower on the group (groupd.hpp); raw lines in digit form
-  (void)gbase;
   g2d_raw_lines_group<GADD>(fq2d_from_fq2(q.x), fq2d_from_fq2(q.y), raw + (size_t)k * MILLER_LINES,
                             scratch + (size_t)k * MILLER_LINES, gl);
 }
@@ -448,37 +440,23 @@ __global__ void __launch_bounds__(64) k_verify_shares_ml(const g1a* __restrict__
   const size_t idx = (size_t)j * n + i;
   uint8_t res = share_precheck(s_status[idx], present == nullptr || present[idx] || i == me, i < n_keys,
                                ct_ok[j] != 0);
-#if HBX_ML_SCALED == 2
   // a proposer with a line whose constant term is 0 (k_normalise_lines; never expected) has no
   // form in lines_u: its checks go to the single-kernel check over `lines`, as a degenerate
   // compressed squaring's do.  force_degen (tests only, hbx_debug_force_degenerate): every
   // force_degen-th proposer is taken for one.
   if (res == HBX_SHARE_VALID && (degen[j] || (force_degen && (j % force_degen) == 0))) res = SHARE_FALLBACK;
-#endif
   if (res == HBX_SHARE_VALID) {
     const g1a sh = S[idx], pki = pk[i];
     const bool skipA = sh.inf || G2pts[2 * j].inf;
     const bool skipB = pki.inf || G2pts[2 * j + 1].inf;
     if (!(skipA && skipB)) {
       lds_u32* slot = (lds_u32*)(park + threadIdx.x);
-#if HBX_ML_SCALED == 2
       // lines divided by their constant term (pairingd.hpp miller_loop2_unit_d): S and -[m] pk_i as they are
       park_put_fqd(slot, 0, fqd_from_fq(sh.x));
       park_put_fqd(slot, 1, fqd_from_fq(sh.y));
       park_put_fqd(slot, 2, fqd_from_fq(pki.x));
       park_put_fqd(slot, 3, fqd_neg(fqd_from_fq(pki.y)));
       const fq12d fd = miller_loop2_unit_d(lines_u[j].h, !skipA, lines_u[j].w, !skipB, slot);
-#elif HBX_ML_SCALED
-      // lines divided by y_P (pairingd.hpp miller_loop2_scaled_d): (x/y, 1/y) of S and of -[m] pk_i
-      park_scaled_points(slot, sh.x, sh.y, sh.inf, pki.x, fq_neg(pki.y), pki.inf);
-      const fq12d fd = miller_loop2_scaled_d(lines[j].h, !skipA, lines[j].w, !skipB, slot);
-#else
-      park_put_fqd(slot, 0, fqd_from_fq(sh.x));
-      park_put_fqd(slot, 1, fqd_from_fq(sh.y));
-      park_put_fqd(slot, 2, fqd_from_fq(pki.x));
-      park_put_fqd(slot, 3, fqd_neg(fqd_from_fq(pki.y)));
-      const fq12d fd = miller_loop2_parked_d(lines[j].h, !skipA, lines[j].w, !skipB, slot);
-#endif
       uint32_t* gf = gslot + (size_t)(blockIdx.y * gridDim.x + blockIdx.x) * (3 * FE1_WORDS * 64) + threadIdx.x;
       s1_put_fq12d<64>(gf, fq12d{fd.c0, fq6d_norm(fd.c1)});
       res = SHARE_PENDING;
@@ -487,13 +465,10 @@ __global__ void __launch_bounds__(64) k_verify_shares_ml(const g1a* __restrict__
   valid[idx] = res;
 }
 
-#ifndef HBX_V3_WAVES
-#define HBX_V3_WAVES 1
-#endif
 // k_verify_shares with THREE lanes per share (pairing3.hpp): 21 checks per wave, ~2.5x lower
 // latency per check.  Used when a launch has too few shares to fill the chip one lane per share
 // (an epoch shard on one of several GPUs).  Same inputs, outputs and own-share semantics.
-__global__ void __launch_bounds__(64, HBX_V3_WAVES) k_verify_shares3(const g1a* __restrict__ S, const int32_t* __restrict__ s_status,
+__global__ void __launch_bounds__(64, 1) k_verify_shares3(const g1a* __restrict__ S, const int32_t* __restrict__ s_status,
                                                        const uint8_t* __restrict__ present,
                                                        const g1a* __restrict__ pk, uint32_t n_keys,
                                                        const g2a* __restrict__ G2pts,
@@ -528,9 +503,6 @@ __global__ void __launch_bounds__(64, HBX_V3_WAVES) k_verify_shares3(const g1a* 
 // proposer j).  Lanes whose status is not SHARE_PENDING have nothing to do.  The last kernel (F5 +
 // F6) turns SHARE_PENDING into HBX_SHARE_VALID / INVALID and,
 // in own-share mode, writes the own lane's verdict as Ciphertext::verify (k_verify_shares).
-#ifndef HBX_FE1_LANE_LDS
-#define HBX_FE1_LANE_LDS 0
-#endif
 template <int STEP>
 __global__ void __launch_bounds__(64) k_fe1(uint32_t* __restrict__ gslot, uint32_t n, uint8_t* __restrict__ valid,
                                             const uint8_t* __restrict__ ct_ok, uint32_t me,
@@ -546,11 +518,7 @@ __global__ void __launch_bounds__(64) k_fe1(uint32_t* __restrict__ gslot, uint32
       ct_valid[j] = !ct_ok[j] ? HBX_CT_UNDECODABLE : st == HBX_SHARE_VALID ? HBX_CT_VALID : HBX_CT_INVALID;
     return;
   }
-#if HBX_FE1_LANE_LDS
-  const lane_lds a{(lds_u32*)slots};  // the slot addressed afresh at every access (fe1d.hpp)
-#else
   lds_u32* a = (lds_u32*)(slots + threadIdx.x);
-#endif
   uint32_t* gf = gslot + (size_t)(blockIdx.y * gridDim.x + blockIdx.x) * (3 * FE1_WORDS * 64) + threadIdx.x;
   uint32_t* gt = gf + FE1_WORDS * 64;
   uint32_t* gg = gt + FE1_WORDS * 64;

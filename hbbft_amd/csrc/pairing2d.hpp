@@ -676,18 +676,12 @@ __device__ __forceinline__ bool final_exp2d_is_one(const slot2<PA>& A, const slo
 // lane 1 x/y.  `neg`: use -P.
 __device__ __forceinline__ fqd point_scalar2d(const g1a& P, bool neg, bool l1) {
   const fq y = neg ? fq_neg(P.y) : P.y;
-#if HBX_ML_INV
+  // the digit-form inversion, out of line (fieldd.hpp fqd_inv_ni): inlined it cost the coin Miller
+  // kernel 4.06 -> 4.14 ms against the 12-limb fq_inv_i, out of line it is neutral to slightly
+  // faster (profiles/r06l_variants.txt)
   bool zero;
-#if HBX_ML_INV == 2
   const fqd yi = fqd_inv_ni(fqd_from_fq(y), zero);
-#else
-  const fqd yi = fqd_inv(fqd_from_fq(y), zero);  // digit form (fieldd.hpp fqd_inv)
-#endif
   return l1 ? fqd_mul(fqd_from_fq(P.x), yi) : yi;
-#else
-  const fq yi = fq_inv_i(y);  // (the digit form inline: coin Miller kernel 4.06 -> 4.14 ms)
-  return fqd_from_fq(l1 ? fq_mul(P.x, yi) : yi);
-#endif
 }
 
 // ---- the coin's check: lines generated on the fly, f split over the pair ----------------------

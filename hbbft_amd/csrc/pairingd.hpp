@@ -293,8 +293,8 @@ HBX_HD void fq6d_mul_acc1(fq6d& acc, const fq6d& a, Y y) {
   acc = fq6d_norm(acc);
 }
 
-// Slot words of the scaled Miller loop (word k at park[k * LDS_FQ12_STRIDE]): 0..55 the points'
-// scalars (park_scaled_points), 56..139 an Fq6 operand streamed into a product (below).
+// Slot words of the parked two-pair Miller loops (word k at park[k * LDS_FQ12_STRIDE]): 0..55 the
+// two G1 points' coordinates (park_put_fqd), 56..139 an Fq6 operand streamed into a product (below).
 constexpr int ML_PARK_Y = 56;
 HBX_HD void park_put_fq2d(lds_u32* park, int word, const fq2d& a) {
 #pragma unroll
@@ -332,34 +332,6 @@ HBX_HD fq12d fq12d_sqr_parked(const fq12d& a, lds_u32* park) {
   return fq12d{fq6d_reduce(fq6d_sub(fq6d_sub(t, ab), fq6d_mul_v(ab))), fq6d_reduce(fq6d_add(ab, ab))};
 }
 
-// miller_loop2_parked_d over lines divided by y_P: the slot holds (x_A / y_A, 1 / y_A,
-// x_B / y_B, 1 / y_B) (park_scaled_points), each line becomes (c0 / y) + (c1 x / y) v + v w and its
-// product costs two Fq-by-Fq2 products for the scaled coefficients instead of one plus the three
-// of the c4 = y term (fq12d_mul_by_01v).  The element differs from miller_loop2_parked_d's by a
-// product of Fq factors (1 / y per line), which the final exponentiation maps to 1: the same verdict.
-HBX_HD fq12d miller_loop2_scaled_d(const line_pre_d* LA, bool useA, const line_pre_d* LB, bool useB,
-                                   lds_u32* park) {
-  fq12d f = fq12d_one();
-  int k = 0;
-#pragma unroll 1
-  for (int i = 62; i >= 0; i--) {
-    if (i != 62) f = fq12d_sqr_parked(f, park);
-    const int steps = ((BLS_X >> i) & 1) ? 4 : 2;  // (A, B) lines of the doubling [+ addition]
-#pragma unroll 1
-    for (int s = 0; s < steps; s++) {
-      const bool b = (s & 1) != 0;
-      const line_pre_d L = ld_uniform((b ? LB : LA) + k);
-      if (b ? useB : useA) {
-        HBX_SEQ();
-        const fqd w = park_get_fqd(park, b ? 2 : 0);
-        const fqd u = park_get_fqd(park, b ? 3 : 1);
-        f = fq12d_mul_by_01v(f, fq2d_mul_fq(L.c0, u), fq2d_mul_fq(L.c1, w));
-      }
-      if (b) k++;
-    }
-  }
-  return fq12d_conj(f);
-}
 // miller_loop2_parked_d over lines divided by their constant term (k_normalise_lines' second
 // table: L.c0 = a = c2 / c0, L.c1 = b = c1 / c0 of the raw line c0 + c1 x v + c2 y v w): the slot
 // holds (x_A, y_A, x_B, y_B) as miller_loop2_parked_d's, each line becomes 1 + (b x) v + (a y) v w
@@ -388,40 +360,6 @@ HBX_HD fq12d miller_loop2_unit_d(const line_pre_d* LA, bool useA, const line_pre
     }
   }
   return fq12d_conj(f);
-}
-// (x / y, 1 / y) of the two affine G1 points into the slot (words 0..3), one Fq inversion for both
-// (Montgomery's trick); a point at infinity contributes 1 (its pair is not used)
-#ifndef HBX_ML_INV
-#define HBX_ML_INV 2  // the scalars' inversion: 0 12-limb (inline), 1 digit form inline, 2 digit form out of line
-#endif
-HBX_HD void park_scaled_points(lds_u32* park, const fq& ax, const fq& ay, bool ainf, const fq& bx, const fq& by,
-                               bool binf) {
-#if HBX_ML_INV
-  // in the digit form throughout (fieldd.hpp fqd_inv; HBX_ML_INV 2: out of line)
-  const fqd ya = ainf ? fqd_const(FQD_ONE) : fqd_from_fq(ay), yb = binf ? fqd_const(FQD_ONE) : fqd_from_fq(by);
-  bool zero;
-#if HBX_ML_INV == 2
-  const fqd inv = fqd_inv_ni(fqd_mul(ya, yb), zero);
-#else
-  const fqd inv = fqd_inv(fqd_mul(ya, yb), zero);
-#endif
-  const fqd ua = fqd_mul(inv, yb), ub = fqd_mul(inv, ya);
-  park_put_fqd(park, 0, fqd_mul(fqd_from_fq(ax), ua));
-  park_put_fqd(park, 1, ua);
-  park_put_fqd(park, 2, fqd_mul(fqd_from_fq(bx), ub));
-  park_put_fqd(park, 3, ub);
-#else
-  // the 12-limb inversion (round 5).  The digit form inlined raised the Miller kernel 8.31 -> 8.48 ms
-  // (profiles/r06k_kernel_stats.txt); out of line (HBX_ML_INV 2, the default) it is neutral to
-  // slightly faster (verify 16.96 -> 16.94 ms, coin 13.37 -> 13.33 ms, profiles/r06l_variants.txt)
-  const fq ya = ainf ? fq_one() : ay, yb = binf ? fq_one() : by;
-  const fq inv = fq_inv_i(fq_mul(ya, yb));
-  const fq ua = fq_mul(inv, yb), ub = fq_mul(inv, ya);
-  park_put_fqd(park, 0, fqd_from_fq(fq_mul(ax, ua)));
-  park_put_fqd(park, 1, fqd_from_fq(ua));
-  park_put_fqd(park, 2, fqd_from_fq(fq_mul(bx, ub)));
-  park_put_fqd(park, 3, fqd_from_fq(ub));
-#endif
 }
 
 // miller_loop_gen_d with (qx, qy, bx, by) parked in this lane's LDS slot (free until the final

@@ -3,7 +3,7 @@ term): the product fq12d_mul_by_1ab (fieldd.hpp), the second normalised table
 (pairing.hpp g2_normalise_line_z2, the routine k_normalise_lines runs per line) and the loop
 miller_loop2_unit_d (pairingd.hpp), compiled for the host with -DHBX_DCHECK
 (tools/hostcheck/linecheck.cpp) and compared with field.hpp's generic tower and with the loop over
-lines divided by y_P.  HBX_DCHECK aborts the process on a product operand digit out of bounds."""
+the first table's lines (miller_loop2_parked_d, the loop k_verify_shares runs).  HBX_DCHECK aborts the process on a product operand digit out of bounds."""
 import ctypes
 import os
 import random
@@ -100,7 +100,7 @@ def _points(rnd, a, valid):
 @pytest.mark.parametrize("jac", [0, 1], ids=["affine", "jacobian"])
 def test_unit_loop_same_verdict_as_scaled_loop(lc, jac):
     """For random G2 and G1 points the loop over lines divided by their constant term and the loop over
-    lines divided by y_P give the same element after the final exponentiation -- 1 for valid pairs,
+    the first table's lines (miller_loop2_parked_d) give the same element after the final exponentiation -- 1 for valid pairs,
     the same element other than 1 for invalid ones; the first-form table out of the combined
     normalisation equals the affine point's, and each second-form (a, b) times the raw c0 gives back
     the raw line.  `jacobian`: QA's raw lines come from a Jacobian representative with Z != 1, as

@@ -136,15 +136,7 @@ int hc_miller2_digit_cmp(const uint8_t* pa, const uint8_t* qa, const uint8_t* pb
   const fq* y = &e2.c0.c0.c0;
   int same_fe = 1;
   for (int i = 0; i < 12; i++) same_fe &= fq_eq(x[i], y[i]) ? 1 : 0;
-  // the loop over lines divided by y_P (miller_loop2_scaled_d, the one-lane Miller kernel): a
-  // different element (Fq factors), the same element after the final exponentiation
-  park_scaled_points(park, PA.x, PA.y, false, PB.x, PB.y, false);
-  const fq12 gs = fq12d_to_fq12(miller_loop2_scaled_d(DA, true, DB, true, park));
-  const fq12 e3 = final_exponentiation(gs);
-  const fq* z = &e3.c0.c0.c0;
-  int same_scaled = 1;
-  for (int i = 0; i < 12; i++) same_scaled &= fq_eq(x[i], z[i]) ? 1 : 0;
-  return same + 2 * same_fe * same_scaled;
+  return same + 2 * same_fe;
 }
 // The final exponentiation as k_fe1's five steps (fe1d.hpp) on host slots, against
 // final_exponentiation_d on the same Miller output: 1 = the same element, + 2 if the verdicts

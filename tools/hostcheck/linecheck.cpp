@@ -52,7 +52,7 @@ void lc_mul_by_1ab(const int32_t* f_, const int32_t* alpha_, const int32_t* beta
 // Both normalised tables of QA and QB off g2_normalise_line_z2 (QA's raw lines made from the
 // Jacobian representative (x z^2, y z^3, z) when jac is set, as k_prepare_lines makes H''s), then
 // the loop over the second table (miller_loop2_unit_d) against the loop over the first
-// (miller_loop2_scaled_d) at (PA, PB).  Returns a bit set, or a negative decode error:
+// (miller_loop2_parked_d, k_verify_shares' loop) at (PA, PB).  Returns a bit set, or a negative decode error:
 //   1  both loops give the same element after the final exponentiation
 //   2  that element is 1 (the check holds)
 //   4  the first table equals g2_normalise_line's of the affine points
@@ -95,12 +95,11 @@ int lc_unit_loop_cmp(const uint8_t* pa, const uint8_t* qa, const uint8_t* pb, co
     }
   }
   static uint32_t park[LDS_FQ12D_DWORDS];
-  park_scaled_points(park, PA.x, PA.y, false, PB.x, PB.y, false);
-  const fq12 e_old = final_exponentiation(fq12d_to_fq12(miller_loop2_scaled_d(D[0], true, D[1], true, park)));
   park_put_fqd(park, 0, fqd_from_fq(PA.x));
   park_put_fqd(park, 1, fqd_from_fq(PA.y));
   park_put_fqd(park, 2, fqd_from_fq(PB.x));
   park_put_fqd(park, 3, fqd_neg(fqd_from_fq(fq_neg(PB.y))));  // a negated digit vector, as the kernel parks -y_pk
+  const fq12 e_old = final_exponentiation(fq12d_to_fq12(miller_loop2_parked_d(D[0], true, D[1], true, park)));
   const fq12 e_new = final_exponentiation(fq12d_to_fq12(miller_loop2_unit_d(U[0], true, U[1], true, park)));
   if (fq12_same(e_old, e_new)) res |= 1;
   if (fq12_is_one(e_new)) res |= 2;

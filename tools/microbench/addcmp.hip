@@ -39,7 +39,7 @@ __device__ __forceinline__ void r16x_clear(round16x& R) {
 }
 __device__ __forceinline__ fqd r16x_run(const round16x& R, int gl) { return fqd_mul(fqd_sel16x(gl, R.a), fqd_sel16x(gl, R.b)); }
 
-// P + Q on the 16 lanes of a group (hash.hpp g2_add_group, add-2007-bl) in five rounds, the same
+// P + Q on the 16 lanes of a group (groupd.hpp g2d_add_group, add-2007-bl) in five rounds, the same
 // special cases as g2_add by exact tests.  Relaxed in and out.
 __device__ __forceinline__ g2jd g2d_add_old(const g2jd& p, const g2jd& q, int gl) {
   if (fq2d_is_zero_mod(p.z)) return q;

@@ -13,17 +13,9 @@ using namespace hbx;
 #ifndef PROBE_WAVES
 #define PROBE_WAVES 1  // min waves per SIMD the kernels are compiled for (2: at most 256 registers)
 #endif
-#ifndef PROBE_LANE_LDS
-#define PROBE_LANE_LDS 1  // 1: the slot addressed afresh (fe1d.hpp lane_lds), 0: a held pointer
-#endif
-#if PROBE_LANE_LDS
-#define PROBE_LDS_SLOT const lane_lds a { (lds_u32*)slots }
-#else
-#define PROBE_LDS_SLOT lds_u32* a = (lds_u32*)(slots + threadIdx.x)
-#endif
 #define PROBE_SLOTS                                                                                   \
   __shared__ uint32_t slots[FE1_WORDS * 64];                                                         \
-  PROBE_LDS_SLOT;                                                                                     \
+  lds_u32* a = (lds_u32*)(slots + threadIdx.x);                                                       \
   uint32_t* gf = g + (size_t)blockIdx.x * (3 * FE1_WORDS * 64) + threadIdx.x;                        \
   uint32_t* gt = gf + FE1_WORDS * 64;                                                                \
   uint32_t* gg = gt + FE1_WORDS * 64;                                                                \

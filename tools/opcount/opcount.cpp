@@ -60,15 +60,9 @@ int main() {
   (void)final_exponentiation_d(fdd, slot);
   const unsigned long long c_fexp_d = hbx_opcount_fqmul;
   fprintf(stderr, "digit tower: miller %llu final_exp %llu (conversions and inversion included)\n", c_miller_d, c_fexp_d);
-  // the one-lane Miller kernel's loops (k_verify_shares_ml), the parking of the points included: over
-  // lines divided by y_P (HBX_ML_SCALED 1; the inversion's divsteps are no Fq products) and over
-  // lines divided by their constant term (HBX_ML_SCALED 2, the default), whose table comes out of
-  // the same normalisation
+  // the one-lane Miller kernel's loop (k_verify_shares_ml), the parking of the points included: over
+  // lines divided by their constant term, whose table comes out of the same normalisation
   static uint32_t park[LDS_FQ12D_DWORDS];
-  hbx_opcount_fqmul = 0;
-  park_scaled_points(park, P.x, P.y, false, nP.x, nP.y, false);
-  (void)miller_loop2_scaled_d(D1, true, D2, true, park);
-  const unsigned long long c_miller_scaled = hbx_opcount_fqmul;
   static line_pre raw[MILLER_LINES], unit[MILLER_LINES];
   static fq2 rc2[MILLER_LINES];
   static line_pre_d U[MILLER_LINES];
@@ -89,9 +83,9 @@ int main() {
   const fq12d fu = miller_loop2_unit_d(U, true, U, true, park);
   const unsigned long long c_miller_unit = hbx_opcount_fqmul;
   const bool ok_unit = fq12_is_one(final_exponentiation(fq12d_to_fq12(fu)));
-  fprintf(stderr, "one-lane Miller kernel: lines / y_P %llu, lines / c0 %llu (check_ok %d); normalising 68 lines: "
+  fprintf(stderr, "one-lane Miller kernel: lines / c0 %llu (check_ok %d); normalising 68 lines: "
                   "one table %llu, both tables %llu (inversions' own products included)\n",
-          c_miller_scaled, c_miller_unit, ok_unit ? 1 : 0, c_norm1, c_norm2);
+          c_miller_unit, ok_unit ? 1 : 0, c_norm1, c_norm2);
   // the coin's signature-share check: pair A over prepared lines, pair B's lines on the fly
   hbx_opcount_fqmul = 0;
   const fq12 fm = miller_loop_mixed(L1, P, true, Q, nP, true);
