@@ -16,6 +16,7 @@
 #include "../../include/hbx.h"
 #include "hbx_kernels.hip"
 #include "broadcast.hpp"
+#include "addplan.hpp"
 #if defined(HBX_TU) && HBX_TU == 0
 #include "_kdecl.hpp"  // the kernels live in translation units 1..6 (tools/build.py)
 #endif
@@ -97,6 +98,13 @@ struct hbx_ctx {
   uint32_t n_shares = 0, verified_p = 0;
   dbuf S, S_status, fallback, valid, shares_own, present_own, gslot;
   dbuf fe1slot;  // one-lane checks: the final exponentiation's global slots F, T, G (fe1d.hpp)
+  uint32_t verify_tiles = 0;  // check blocks of the last share-check launch (hbx_get_verify_tiles_used)
+  // hbx_add_dec_shares_d: the candidates of an add, decoded and checked apart from the epoch's
+  // matrix (same p x n layout; only the add's tiles are ever written or read), the positions of the
+  // add as the tile launch's present mask (all 0 between calls; add_mask_m = the bytes known to be
+  // 0), and the host form's staging
+  dbuf add_S, add_status, add_valid, add_mask, add_zero, add_shares, add_dst;
+  size_t add_mask_m = 0;
   uint32_t force_fallback = 0;  // hbx_debug_force_fallback (tests only)
   uint32_t force_degen = 0;  // hbx_debug_force_degenerate (tests only)
   // the combine's window tables (g1d.hpp; built by k_prepare_lines in the fused epoch call only):
@@ -319,7 +327,7 @@ static int launch_batch_columns(hbx_ctx* c, hipStream_t s, const uint8_t* d_pres
     // verdict byte in b_pass (1 = the equation holds); the identity cases are check2_g6d's
     hipLaunchKernelGGL(k_verify_shares6, dim3(1, p), dim3(64), 0, s, c->b_A.as<g1a>(), c->b_zero.as<int32_t>(), nullptr,
                        c->b_B.as<g1a>(), 1u, c->G2pts.as<g2a>(), c->lines_d.as<line_block_d>(), c->b_cand.as<uint8_t>(),
-                       1u, c->b_pass.as<uint8_t>(), UINT32_MAX, nullptr, 1u);
+                       1u, c->b_pass.as<uint8_t>(), UINT32_MAX, nullptr, 1u, nullptr);
     hipLaunchKernelGGL(k_batch_mask, dim3((p + 63) / 64), dim3(64), 0, s, c->b_cls0.as<uint8_t>(), c->b_pass.as<uint8_t>(),
                        c->ct_ok.as<uint8_t>(), p, c->b_cls.as<uint8_t>(), c->b_ctok.as<uint8_t>(),
                        c->b_stats.as<uint32_t>());
@@ -1012,6 +1020,56 @@ int hbx_prepare_ciphertexts(hbx_ctx* c, const uint8_t* u_comp, const uint8_t* v_
   return HBX_OK;
 }
 
+// The share-check launch at `lanes` lanes per check (7: the one-lane check as one kernel) over
+// `grid` blocks: the tiles (chunks, p) of a matrix verification (tiles = nullptr), or the listed
+// tiles of an add, grid (T, 1) (addplan.hpp).  `me` / `ctv`: own-share mode's lane and where its
+// verdict goes as Ciphertext::verify.
+static int launch_share_checks(hbx_ctx* c, hipStream_t s, int lanes, dim3 grid, const uint2* tiles, const g1a* S,
+                               const int32_t* S_status, const uint8_t* d_present, uint8_t* vd, const uint8_t* ctok,
+                               uint32_t n, uint32_t me, uint8_t* ctv) {
+  const size_t blocks = (size_t)grid.x * grid.y;
+  c->fb_last = nullptr;  // set again below by the one-lane path, the only one with a fallback
+  if (lanes == 2) {
+    // global slots of the final exponentiation: 2 x 78 dwords per lane of the launch
+    if (!c->gslot.ensure(blocks * 64 * 2 * LDS_FQ6D_PACKED * 4))
+      return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_verify_dec_shares_d: out of device memory (slots)");
+    hipLaunchKernelGGL(k_verify_shares2, grid, dim3(64), 0, s, S, S_status, d_present, c->pk_m.as<g1a>(), c->n_keys,
+                       c->G2pts.as<g2a>(), c->lines_d.as<line_block_d>(), ctok, n, vd, me, ctv, c->gslot.as<uint32_t>(),
+                       tiles);
+  } else if (lanes == 6)
+    hipLaunchKernelGGL(k_verify_shares6, grid, dim3(64), 0, s, S, S_status, d_present, c->pk_m.as<g1a>(), c->n_keys,
+                       c->G2pts.as<g2a>(), c->lines_d.as<line_block_d>(), ctok, n, vd, me, ctv, 0u, tiles);
+  else if (lanes == 3)
+    hipLaunchKernelGGL(k_verify_shares3, grid, dim3(64), 0, s, S, S_status, d_present, c->pk_m.as<g1a>(), c->n_keys,
+                       c->G2pts.as<g2a>(), c->lines_d.as<line_block_d>(), ctok, n, vd, me, ctv, tiles);
+  else if (lanes == 7)  // the one-lane check as one kernel (final exponentiation through call frames)
+    hipLaunchKernelGGL(k_verify_shares, grid, dim3(64), 0, s, S, S_status, d_present, c->pk_m.as<g1a>(), c->n_keys,
+                       c->G2pts.as<g2a>(), c->lines_d.as<line_block_d>(), ctok, n, vd, me, ctv, 0u, nullptr, tiles);
+  else {
+    // one lane per check: the Miller loops, then the final exponentiation's seven steps as four
+    // kernels over per-lane slots (fe1d.hpp: no Fq12 ever crosses a call frame)
+    if (!c->fe1slot.ensure(blocks * 64 * 3 * FE1_WORDS * 4))
+      return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_verify_dec_shares_d: out of device memory (slots)");
+    uint32_t* gs = c->fe1slot.as<uint32_t>();
+    if (!c->fb_lanes.ensure(4)) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_verify_dec_shares_d: out of device memory");
+    HIPCHK(c, hipMemsetAsync(c->fb_lanes.p, 0, 4, s));
+    c->fb_last = &c->fb_lanes;
+    hipLaunchKernelGGL(k_verify_shares_ml, grid, dim3(64), 0, s, S, S_status, d_present, c->pk_m.as<g1a>(), c->n_keys,
+                       c->G2pts.as<g2a>(), c->lines_d.as<line_block_d>(), ctok, n, vd, me, gs,
+                       c->lines_u.as<line_block_d>(), c->line_degen.as<uint8_t>(), c->force_degen, tiles);
+    hipLaunchKernelGGL(k_fe1<0>, grid, dim3(64), 0, s, gs, n, vd, ctok, me, ctv, c->force_fallback, tiles);
+    hipLaunchKernelGGL(k_fe1<1>, grid, dim3(64), 0, s, gs, n, vd, ctok, me, ctv, c->force_fallback, tiles);  // F1 + F2
+    hipLaunchKernelGGL(k_fe1<3>, grid, dim3(64), 0, s, gs, n, vd, ctok, me, ctv, c->force_fallback, tiles);  // F3 + F4
+    hipLaunchKernelGGL(k_fe1<5>, grid, dim3(64), 0, s, gs, n, vd, ctok, me, ctv, c->force_fallback, tiles);  // F5 + F6
+    // lanes whose compressed squarings met g3 = 0, and the lanes of a proposer with a line whose
+    // constant term is 0 (neither ever expected): the single-kernel check
+    hipLaunchKernelGGL(k_verify_shares, grid, dim3(64), 0, s, S, S_status, d_present, c->pk_m.as<g1a>(), c->n_keys,
+                       c->G2pts.as<g2a>(), c->lines_d.as<line_block_d>(), ctok, n, vd, me, ctv, 1u,
+                       c->fb_lanes.as<uint32_t>(), tiles);
+  }
+  return HBX_OK;
+}
+
 // Share checks of the prepared ciphertexts.  `predecoded`: the fused epoch call (hbx_decrypt_epoch_d)
 // had prepare_impl decode exactly these shares into S / S_status already.
 static int verify_impl(hbx_ctx* c, const uint8_t* d_shares, const uint8_t* d_present, uint32_t n, uint32_t p,
@@ -1072,63 +1130,13 @@ static int verify_impl(hbx_ctx* c, const uint8_t* d_shares, const uint8_t* d_pre
                       : waves2 <= fill ? 2
                                        : 3;
     c->lanes_used = lanes;
-    c->fb_last = nullptr;  // set again below by the one-lane path, the only one with a fallback
-    if (lanes == 2) {
-      // global slots of the final exponentiation: 2 x 78 dwords per lane of the launch
-      const size_t glanes = (size_t)((n + 31) / 32) * p * 64;
-      if (!c->gslot.ensure(glanes * 2 * LDS_FQ6D_PACKED * 4))
-        return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_verify_dec_shares_d: out of device memory (slots)");
-      hipLaunchKernelGGL(k_verify_shares2, dim3((n + 31) / 32, p), dim3(64), 0, s, c->S.as<g1a>(),
-                         c->S_status.as<int32_t>(), d_present, c->pk_m.as<g1a>(), c->n_keys, c->G2pts.as<g2a>(),
-                         c->lines_d.as<line_block_d>(), ctok, n, c->valid.as<uint8_t>(),
-                         own ? c->own_me : UINT32_MAX,
-                         (own && !c->ct_known) ? c->ct_valid.as<uint8_t>() : nullptr, c->gslot.as<uint32_t>());
-    }
-    else if (lanes == 6)
-      hipLaunchKernelGGL(k_verify_shares6, dim3((n + G6_PER_WAVE - 1) / G6_PER_WAVE, p), dim3(64), 0, s,
-                         c->S.as<g1a>(), c->S_status.as<int32_t>(), d_present, c->pk_m.as<g1a>(), c->n_keys,
-                         c->G2pts.as<g2a>(), c->lines_d.as<line_block_d>(), ctok, n,
-                         c->valid.as<uint8_t>(), own ? c->own_me : UINT32_MAX,
-                         (own && !c->ct_known) ? c->ct_valid.as<uint8_t>() : nullptr, 0u);
-    else if (lanes == 3)
-      hipLaunchKernelGGL(k_verify_shares3, dim3((n + G3_PER_WAVE - 1) / G3_PER_WAVE, p), dim3(64), 0, s,
-                         c->S.as<g1a>(), c->S_status.as<int32_t>(), d_present, c->pk_m.as<g1a>(), c->n_keys,
-                         c->G2pts.as<g2a>(), c->lines_d.as<line_block_d>(), ctok, n,
-                         c->valid.as<uint8_t>(), own ? c->own_me : UINT32_MAX,
-                         (own && !c->ct_known) ? c->ct_valid.as<uint8_t>() : nullptr);
-    else if (lanes == 7)  // the one-lane check as one kernel (final exponentiation through call frames)
-      hipLaunchKernelGGL(k_verify_shares, dim3((n + 63) / 64, p), dim3(64), 0, s, c->S.as<g1a>(),
-                         c->S_status.as<int32_t>(), d_present, c->pk_m.as<g1a>(), c->n_keys, c->G2pts.as<g2a>(),
-                         c->lines_d.as<line_block_d>(), ctok, n, c->valid.as<uint8_t>(),
-                         own ? c->own_me : UINT32_MAX,
-                         (own && !c->ct_known) ? c->ct_valid.as<uint8_t>() : nullptr, 0u, nullptr);
-    else {
-      // one lane per check: the Miller loops, then the final exponentiation's seven steps as four
-      // kernels over per-lane slots (fe1d.hpp: no Fq12 ever crosses a call frame)
-      const dim3 grid((n + 63) / 64, p);
-      if (!c->fe1slot.ensure((size_t)grid.x * grid.y * 64 * 3 * FE1_WORDS * 4))
-        return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_verify_dec_shares_d: out of device memory (slots)");
-      uint8_t* ctv = (own && !c->ct_known) ? c->ct_valid.as<uint8_t>() : nullptr;
-      const uint32_t me = own ? c->own_me : UINT32_MAX;
-      uint32_t* gs = c->fe1slot.as<uint32_t>();
-      if (!c->fb_lanes.ensure(4)) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_verify_dec_shares_d: out of device memory");
-      HIPCHK(c, hipMemsetAsync(c->fb_lanes.p, 0, 4, s));
-      c->fb_last = &c->fb_lanes;
-      hipLaunchKernelGGL(k_verify_shares_ml, grid, dim3(64), 0, s, c->S.as<g1a>(), c->S_status.as<int32_t>(),
-                         d_present, c->pk_m.as<g1a>(), c->n_keys, c->G2pts.as<g2a>(), c->lines_d.as<line_block_d>(),
-                         ctok, n, c->valid.as<uint8_t>(), me, gs, c->lines_u.as<line_block_d>(),
-                         c->line_degen.as<uint8_t>(), c->force_degen);
-      uint8_t* vd = c->valid.as<uint8_t>();
-      hipLaunchKernelGGL(k_fe1<0>, grid, dim3(64), 0, s, gs, n, vd, ctok, me, ctv, c->force_fallback);
-      hipLaunchKernelGGL(k_fe1<1>, grid, dim3(64), 0, s, gs, n, vd, ctok, me, ctv, c->force_fallback);  // F1 + F2
-      hipLaunchKernelGGL(k_fe1<3>, grid, dim3(64), 0, s, gs, n, vd, ctok, me, ctv, c->force_fallback);  // F3 + F4
-      hipLaunchKernelGGL(k_fe1<5>, grid, dim3(64), 0, s, gs, n, vd, ctok, me, ctv, c->force_fallback);  // F5 + F6
-      // lanes whose compressed squarings met g3 = 0, and the lanes of a proposer with a line whose
-      // constant term is 0 (neither ever expected): the single-kernel check
-      hipLaunchKernelGGL(k_verify_shares, grid, dim3(64), 0, s, c->S.as<g1a>(), c->S_status.as<int32_t>(), d_present,
-                         c->pk_m.as<g1a>(), c->n_keys, c->G2pts.as<g2a>(), c->lines_d.as<line_block_d>(), ctok, n, vd,
-                         me, ctv, 1u, c->fb_lanes.as<uint32_t>());
-    }
+    const uint32_t per = lanes == 2 ? 32u : lanes == 6 ? (uint32_t)G6_PER_WAVE : lanes == 3 ? (uint32_t)G3_PER_WAVE : 64u;
+    c->verify_tiles = (uint32_t)((n + per - 1) / per) * p;
+    if (int rc = launch_share_checks(c, s, lanes, dim3((n + per - 1) / per, p), nullptr, c->S.as<g1a>(),
+                                     c->S_status.as<int32_t>(), d_present, c->valid.as<uint8_t>(), ctok, n,
+                                     own ? c->own_me : UINT32_MAX,
+                                     (own && !c->ct_known) ? c->ct_valid.as<uint8_t>() : nullptr))
+      return rc;
   }
   HIPCHK(c, hipGetLastError());
   c->ct_known = true;
@@ -2428,15 +2436,38 @@ int hbx_get_ct_valid_d(hbx_ctx* c, uint8_t* d_ct_valid, void* stream) {
   return HBX_OK;
 }
 
-int hbx_combine_decrypt_d(hbx_ctx* c, uint32_t t, uint8_t* d_out_blob, int32_t* d_status, void* stream) {
-  if (!c || t == 0 || t > (uint32_t)COMBINE_MAX_T || !d_out_blob)
+// The combine of every proposer (cols = nullptr), or of the `ncols` listed ones: the blocks of
+// proposer cols[b] only, so no other status entry or plaintext range is written.
+static int combine_impl(hbx_ctx* c, uint32_t t, uint8_t* d_out_blob, int32_t* d_status, void* stream,
+                        const uint32_t* cols, uint32_t ncols) {
+  if (!c || t == 0 || t > (uint32_t)COMBINE_MAX_T || !d_out_blob || (ncols && !cols))
     return fail(c, HBX_E_INVALID_ARG, "hbx_combine_decrypt_d: bad args");
   if (c->n_shares == 0 || c->p_ct == 0 || !c->ct_known || c->verified_p != c->p_ct)
     return fail(c, HBX_E_NO_CIPHERTEXTS, "no verified shares for the prepared ciphertexts");
+  const uint32_t p = c->p_ct;
+  if (cols) {
+    std::vector<uint8_t> seen(p, 0);
+    for (uint32_t k = 0; k < ncols; k++) {
+      if (cols[k] >= p || seen[cols[k]])
+        return fail(c, HBX_E_INVALID_ARG, "hbx_combine_decrypt_cols_d: cols[%u] = %u is %s", k, cols[k],
+                    cols[k] >= p ? "not a prepared proposer" : "listed twice");
+      seen[cols[k]] = 1;
+    }
+    if (ncols == 0) return HBX_OK;
+  }
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = pick(c, stream);
   stream_scope ss_{c, s};
-  const uint32_t p = c->p_ct;
+  // the listed columns, consumed before the call returns (pinned staging, as the ragged descriptors)
+  const uint32_t* d_cols = nullptr;
+  const uint32_t pl = cols ? ncols : p;  // proposers of this launch
+  if (cols) {
+    uint8_t* pin = rg_begin(c, (size_t)ncols * 4);
+    if (!pin) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_combine_decrypt_cols_d: out of memory (staging)");
+    memcpy(pin, cols, (size_t)ncols * 4);
+    if (int rc = rg_upload(c, (size_t)ncols * 4, s)) return rc;
+    d_cols = c->rg_dev.as<uint32_t>();
+  }
   if (!c->keys.ensure((size_t)p * 32) || !c->status.ensure((size_t)p * 4))
     return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_combine_decrypt_d: out of device memory");
   {
@@ -2444,34 +2475,53 @@ int hbx_combine_decrypt_d(hbx_ctx* c, uint32_t t, uint8_t* d_out_blob, int32_t* 
     // a quad of lanes per GLV term over one-wave blocks when that still leaves at most one wave per
     // SIMD (an epoch shard; k_combine_q), else one lane per term in one block per proposer
     const uint32_t nb = (2 * t + COMBQ_TERMS - 1) / COMBQ_TERMS;
-    const bool quads = combine_quads(c, t, p);
+    const bool quads = combine_quads(c, t, pl);
     // terms without tables, counted per proposer (every block writes its entry)
     if (!c->comb_slow.ensure((size_t)p * 4)) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_combine_decrypt_d: out of device memory");
     c->comb_slow_p = p;
+    if (cols) HIPCHK(c, hipMemsetAsync(c->comb_slow.p, 0, (size_t)p * 4, s));  // only the listed entries are written
     // window tables of the last fused prepare, if they are of these shares
     const bool tabs = c->tab_ready && c->tab_n == c->n_shares && c->tab_p == p;
     if (quads) {
       if (!c->comb_partial.ensure((size_t)p * nb * sizeof(g1j)) || !c->comb_done.ensure((size_t)p * 4))
         return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_combine_decrypt_d: out of device memory");
       HIPCHK(c, hipMemsetAsync(c->comb_done.p, 0, (size_t)p * 4, s));
-      hipLaunchKernelGGL(k_combine_q, dim3(nb, p), dim3(64), 0, s, c->valid.as<uint8_t>(), c->S.as<g1a>(),
+      hipLaunchKernelGGL(k_combine_q, dim3(nb, pl), dim3(64), 0, s, c->valid.as<uint8_t>(), c->S.as<g1a>(),
                          c->n_shares, t, c->ct_valid.as<uint8_t>(), c->keys.as<uint32_t>(), c->status.as<int32_t>(),
-                         c->digest, c->comb_partial.as<g1j>(), c->comb_done.as<uint32_t>(), c->comb_slow.as<uint32_t>());
+                         c->digest, c->comb_partial.as<g1j>(), c->comb_done.as<uint32_t>(), c->comb_slow.as<uint32_t>(),
+                         d_cols);
     } else
-    hipLaunchKernelGGL(k_combine, dim3(p), dim3(COMBINE_THREADS), 0, s, c->valid.as<uint8_t>(), c->S.as<g1a>(),
+    hipLaunchKernelGGL(k_combine, dim3(pl), dim3(COMBINE_THREADS), 0, s, c->valid.as<uint8_t>(), c->S.as<g1a>(),
                        c->n_shares, t, c->ct_valid.as<uint8_t>(), c->keys.as<uint32_t>(), c->status.as<int32_t>(),
                        c->digest, tabs ? c->comb_tab.as<g1jd>() : nullptr, c->comb_tab_ok.as<uint8_t>(),
-                       tabs ? c->tab_cap : 0u, c->tab_me, c->tab_form, c->comb_slow.as<uint32_t>());
+                       tabs ? c->tab_cap : 0u, c->tab_me, c->tab_form, c->comb_slow.as<uint32_t>(), d_cols);
   }
   HIPCHK(c, hipGetLastError());
   const uint64_t blocks = (c->max_v_len + 15) / 16;
   if (blocks) {
-    hipLaunchKernelGGL(k_keystream_xor, dim3((unsigned)((blocks + 63) / 64), p), dim3(64), 0, s,
-                       c->keys.as<uint32_t>(), c->status.as<int32_t>(), c->d_v_blob, c->d_v_off, d_out_blob);
+    hipLaunchKernelGGL(k_keystream_xor, dim3((unsigned)((blocks + 63) / 64), pl), dim3(64), 0, s,
+                       c->keys.as<uint32_t>(), c->status.as<int32_t>(), c->d_v_blob, c->d_v_off, d_out_blob, d_cols);
     HIPCHK(c, hipGetLastError());
   }
-  if (d_status) HIPCHK(c, hipMemcpyAsync(d_status, c->status.p, (size_t)p * 4, hipMemcpyDeviceToDevice, s));
+  if (d_status && !cols) HIPCHK(c, hipMemcpyAsync(d_status, c->status.p, (size_t)p * 4, hipMemcpyDeviceToDevice, s));
+  if (d_status && cols) {
+    hipLaunchKernelGGL(k_scatter_cols, dim3((ncols + 63) / 64), dim3(64), 0, s, c->status.as<int32_t>(), d_cols, ncols,
+                       d_status);
+    HIPCHK(c, hipGetLastError());
+  }
   return HBX_OK;
+}
+
+int hbx_combine_decrypt_d(hbx_ctx* c, uint32_t t, uint8_t* d_out_blob, int32_t* d_status, void* stream) {
+  return combine_impl(c, t, d_out_blob, d_status, stream, nullptr, 0);
+}
+
+int hbx_combine_decrypt_cols_d(hbx_ctx* c, uint32_t t, const uint32_t* cols, uint32_t ncols, uint8_t* d_out_blob,
+                               int32_t* d_status, void* stream) {
+  if (!c || (!cols && ncols)) return fail(c, HBX_E_INVALID_ARG, "hbx_combine_decrypt_cols_d: bad args");
+  if (ncols == 0) return HBX_OK;
+  static const uint32_t none = 0;
+  return combine_impl(c, t, d_out_blob, d_status, stream, cols ? cols : &none, ncols);
 }
 
 int hbx_decrypt_epoch_d(hbx_ctx* c, const uint8_t* d_u_comp, const uint8_t* d_v_blob, const uint64_t* d_v_off,
@@ -2516,6 +2566,150 @@ int hbx_combine_decrypt(hbx_ctx* c, uint32_t t, uint8_t* out_blob, int32_t* stat
   HIPCHK(c, hipMemcpyAsync(st.data(), c->status.p, (size_t)c->p_ct * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (status) memcpy(status, st.data(), st.size() * 4);
+  return HBX_OK;
+}
+
+// ---- incremental share verification (include/hbx.h) ---------------------------------------------
+static_assert(hbx_addplan::SHAPE_SENDERS[2] == (uint32_t)G3_PER_WAVE && hbx_addplan::SHAPE_SENDERS[3] == (uint32_t)G6_PER_WAVE &&
+                  hbx_addplan::FILL_WAVES == (size_t)VERIFY_FILL_WAVES && sizeof(hbx_addplan::tile) == sizeof(uint2),
+              "addplan.hpp restates the check kernels' tile shapes");
+
+int hbx_add_dec_shares_d(hbx_ctx* c, const uint8_t* d_shares48, const uint32_t* proposer, const uint32_t* sender,
+                         uint32_t count, uint32_t n, uint8_t* d_status, void* stream) {
+  if (!c || n == 0 || (count && (!d_shares48 || !proposer || !sender)))
+    return fail(c, HBX_E_INVALID_ARG, "hbx_add_dec_shares_d: bad args");
+  if (c->n_keys == 0) return fail(c, HBX_E_NO_KEYS, "hbx_set_pk_shares has not been called");
+  if (c->p_ct == 0) return fail(c, HBX_E_NO_CIPHERTEXTS, "hbx_add_dec_shares_d: no ciphertexts prepared");
+  const uint32_t p = c->p_ct;
+  const bool established = c->n_shares != 0 && c->verified_p == p;
+  if (established && n != c->n_shares)
+    return fail(c, HBX_E_INVALID_ARG, "hbx_add_dec_shares_d: n=%u but the epoch's matrix has n=%u", n, c->n_shares);
+  const uint32_t me = (c->own_ready && c->own_me < n) ? c->own_me : UINT32_MAX;
+  hbx_addplan::plan pl;
+  switch (hbx_addplan::build(proposer, sender, count, n, p, me, pl)) {
+    case hbx_addplan::PLAN_BAD_PROPOSER:
+      return fail(c, HBX_E_INVALID_ARG, "hbx_add_dec_shares_d: a proposer index >= p=%u", p);
+    case hbx_addplan::PLAN_DUPLICATE:
+      return fail(c, HBX_E_INVALID_ARG, "hbx_add_dec_shares_d: the same (proposer, sender) twice in one call");
+    case hbx_addplan::PLAN_OWN_SENDER:
+      return fail(c, HBX_E_INVALID_ARG, "hbx_add_dec_shares_d: sender %u is this node (own-share mode)", me);
+    default:
+      break;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t m = (size_t)n * p;
+  if (!established) {
+    // the matrix call with every share absent: own-share mode's entries and checks, a deferred
+    // Ciphertext::verify, the batched mode's call index -- whatever that call does on this context
+    if (!c->add_zero.ensure(m * 49)) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_add_dec_shares_d: out of device memory");
+    hipStream_t s0 = pick(c, stream);
+    {
+      stream_scope ss0_{c, s0};
+      HIPCHK(c, hipMemsetAsync(c->add_zero.p, 0, m * 49, s0));
+    }
+    int rc = verify_impl(c, c->add_zero.as<uint8_t>(), c->add_zero.as<uint8_t>() + m * 48, n, p, nullptr, stream, false);
+    if (rc) return rc;
+  }
+  if (count == 0) return HBX_OK;
+  hipStream_t s = pick(c, stream);
+  stream_scope ss_{c, s};
+  if (!c->add_S.ensure(m * sizeof(g1a)) || !c->add_status.ensure(m * 4) || !c->add_valid.ensure(m) ||
+      !c->add_mask.ensure(m))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_add_dec_shares_d: out of device memory");
+  if (c->add_mask_m < m) {  // a new buffer, or one an interrupted call left marked
+    HIPCHK(c, hipMemsetAsync(c->add_mask.p, 0, c->add_mask.cap, s));
+  }
+  c->add_mask_m = 0;
+  // lanes per check from what is live: the matrix call's ladder over the touched-tile counts
+  const int lanes = c->verify_lanes ? c->verify_lanes : hbx_addplan::lanes_of(pl);
+  const std::vector<hbx_addplan::tile>& tiles = pl.tiles[hbx_addplan::shape_of_lanes(lanes)];
+  // the items and the tile list, consumed before the call returns (pinned staging, one upload)
+  const size_t items_bytes = (size_t)count * sizeof(uint2), tiles_bytes = tiles.size() * sizeof(uint2);
+  uint8_t* pin = rg_begin(c, items_bytes + tiles_bytes);
+  if (!pin) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_add_dec_shares_d: out of memory (staging)");
+  uint2* it = reinterpret_cast<uint2*>(pin);
+  for (uint32_t k = 0; k < count; k++) it[k] = make_uint2(proposer[k], sender[k]);
+  if (tiles_bytes) memcpy(pin + items_bytes, tiles.data(), tiles_bytes);
+  if (int rc = rg_upload(c, items_bytes + tiles_bytes, s)) return rc;
+  const uint2* d_items = c->rg_dev.as<uint2>();
+  const uint2* d_tiles = reinterpret_cast<const uint2*>(c->rg_dev.as<uint8_t>() + items_bytes);
+  c->tab_ready = false;  // S is about to hold other shares than the tables were made from
+  const unsigned item_blocks = (count + 255) / 256;
+  {
+    timed t_(c, HBX_K_VERIFY_SHARES, s);
+    c->verify_tiles = (uint32_t)tiles.size();
+    if (pl.live) {
+      hipLaunchKernelGGL(k_add_decode, dim3(item_blocks), dim3(256), 0, s, d_shares48, d_items, count, n,
+                         c->add_S.as<g1a>(), c->add_status.as<int32_t>(), c->add_mask.as<uint8_t>());
+      HIPCHK(c, hipGetLastError());
+      c->lanes_used = lanes;
+      // the add's own items always run the per-share checks (ct_ok, not a batched call's gate); the
+      // own lane and the ciphertexts were decided when the matrix was established
+      if (int rc = launch_share_checks(c, s, lanes, dim3((unsigned)tiles.size(), 1), d_tiles, c->add_S.as<g1a>(),
+                                       c->add_status.as<int32_t>(), c->add_mask.as<uint8_t>(),
+                                       c->add_valid.as<uint8_t>(), c->ct_ok.as<uint8_t>(), n, UINT32_MAX, nullptr))
+        return rc;
+      HIPCHK(c, hipGetLastError());
+    } else {
+      c->fb_last = nullptr;
+    }
+    hipLaunchKernelGGL(k_add_merge, dim3(item_blocks), dim3(256), 0, s, d_items, count, n, c->add_S.as<g1a>(),
+                       c->add_status.as<int32_t>(), c->add_valid.as<uint8_t>(), c->add_mask.as<uint8_t>(),
+                       c->ct_valid.as<uint8_t>(), c->S.as<g1a>(), c->S_status.as<int32_t>(), c->valid.as<uint8_t>(),
+                       d_status);
+  }
+  HIPCHK(c, hipGetLastError());
+  c->add_mask_m = c->add_mask.cap;
+  return HBX_OK;
+}
+
+int hbx_add_dec_shares(hbx_ctx* c, const uint8_t* shares48, const uint32_t* proposer, const uint32_t* sender,
+                       uint32_t count, uint32_t n, uint8_t* status) {
+  if (!c || n == 0 || (count && (!shares48 || !proposer || !sender)))
+    return fail(c, HBX_E_INVALID_ARG, "hbx_add_dec_shares: bad args");
+  HIPCHK(c, hipSetDevice(c->device));
+  stream_scope ss_{c, pick(c, c->stream)};
+  if (!c->add_shares.ensure((size_t)count * 48) || !c->add_dst.ensure(count))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_add_dec_shares: out of device memory");
+  if (count) HIPCHK(c, hipMemcpyAsync(c->add_shares.p, shares48, (size_t)count * 48, hipMemcpyHostToDevice, c->stream));
+  int rc = hbx_add_dec_shares_d(c, c->add_shares.as<uint8_t>(), proposer, sender, count, n, c->add_dst.as<uint8_t>(),
+                                c->stream);
+  if (rc) return rc;
+  std::vector<uint8_t> st(count);
+  if (count) HIPCHK(c, hipMemcpyAsync(st.data(), c->add_dst.p, count, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (status && count) memcpy(status, st.data(), count);
+  return HBX_OK;
+}
+
+uint32_t hbx_get_verify_tiles_used(const hbx_ctx* c) { return c ? c->verify_tiles : 0; }
+
+int hbx_combine_decrypt_cols(hbx_ctx* c, uint32_t t, const uint32_t* cols, uint32_t ncols, uint8_t* out_blob,
+                             int32_t* status) {
+  if (!c || !out_blob || (!cols && ncols)) return fail(c, HBX_E_INVALID_ARG, "hbx_combine_decrypt_cols: bad args");
+  if (ncols == 0) return HBX_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  stream_scope ss_{c, pick(c, c->stream)};
+  if (c->p_ct == 0) return fail(c, HBX_E_NO_CIPHERTEXTS, "no ciphertexts prepared");
+  std::vector<uint64_t> off(c->p_ct + 1);
+  HIPCHK(c, hipMemcpyAsync(off.data(), c->d_v_off, off.size() * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint64_t total = off[c->p_ct];
+  if (!c->out_own.ensure(total ? total : 16)) return fail(c, HBX_E_OUT_OF_MEMORY, "out of device memory");
+  int rc = hbx_combine_decrypt_cols_d(c, t, cols, ncols, c->out_own.as<uint8_t>(), nullptr, c->stream);
+  if (rc) return rc;
+  std::vector<int32_t> st(c->p_ct);
+  HIPCHK(c, hipMemcpyAsync(st.data(), c->status.p, (size_t)c->p_ct * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  // the listed proposers' entries and ranges only: nothing else of the caller's buffers is written
+  // (a proposer that did not decrypt has no plaintext: its range stays as the caller had it)
+  for (uint32_t k = 0; k < ncols; k++) {
+    const uint64_t a = off[cols[k]], b = off[cols[k] + 1];
+    if (status) status[cols[k]] = st[cols[k]];
+    if (st[cols[k]] == 0 && b > a)
+      HIPCHK(c, hipMemcpyAsync(out_blob + a, c->out_own.as<uint8_t>() + a, b - a, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return HBX_OK;
 }
 

@@ -67,6 +67,16 @@ constexpr uint8_t SHARE_PENDING = 0xFE;
 // again by the single-kernel check (k_verify_shares with fallback_only).
 constexpr uint8_t SHARE_FALLBACK = 0xFD;
 
+// Tile of a share-check block: (sender chunk x, proposer j).  A matrix verification launches the
+// grid (chunks, p) and passes tiles = nullptr; hbx_add_dec_shares_d launches one block per touched
+// tile, grid (T, 1), and the block reads its coordinates from tiles[blockIdx.x] -- a kernel argument
+// indexed by the block id, so one scalar load per block and no vector register.  The per-block
+// slots (fe1slot, gslot) stay indexed by blockIdx.y * gridDim.x + blockIdx.x, which is the list
+// position in a tile launch.
+__device__ __forceinline__ uint2 share_tile(const uint2* __restrict__ tiles) {
+  return tiles ? tiles[blockIdx.x] : make_uint2(blockIdx.x, blockIdx.y);
+}
+
 // e(PA, QA) * e(PB, QB) == 1 with identity handling (pairing with the identity is 1).
 __device__ __forceinline__ bool check2(const line_pre* LA, const g1a& PA, bool qa_inf,
                                        const line_pre* LB, const g1a& PB, bool qb_inf) {
@@ -385,10 +395,12 @@ __global__ void __launch_bounds__(64) k_verify_shares(const g1a* __restrict__ S,
                                                       const uint8_t* __restrict__ ct_ok, uint32_t n,
                                                       uint8_t* __restrict__ valid, uint32_t me,
                                                       uint8_t* __restrict__ ct_valid, uint32_t fallback_only,
-                                                      uint32_t* __restrict__ fallback_lanes) {
+                                                      uint32_t* __restrict__ fallback_lanes,
+                                                      const uint2* __restrict__ tiles) {
   __shared__ uint32_t gslots[LDS_FQ12D_DWORDS * LDS_FQ12_STRIDE];  // final-exp base, one slot per lane
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t j = blockIdx.y;
+  const uint2 tl = share_tile(tiles);
+  const uint32_t i = tl.x * blockDim.x + threadIdx.x;
+  const uint32_t j = tl.y;
   if (i >= n) return;
   const size_t idx = (size_t)j * n + i;
   if (fallback_only) {
@@ -432,10 +444,12 @@ __global__ void __launch_bounds__(64) k_verify_shares_ml(const g1a* __restrict__
                                                          uint8_t* __restrict__ valid, uint32_t me,
                                                          uint32_t* __restrict__ gslot,
                                                          const line_block_d* __restrict__ lines_u,
-                                                         const uint8_t* __restrict__ degen, uint32_t force_degen) {
+                                                         const uint8_t* __restrict__ degen, uint32_t force_degen,
+                                                         const uint2* __restrict__ tiles) {
   __shared__ uint32_t park[LDS_FQ12D_DWORDS * LDS_FQ12_STRIDE];  // the G1 points, one slot per lane
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t j = blockIdx.y;
+  const uint2 tl = share_tile(tiles);
+  const uint32_t i = tl.x * blockDim.x + threadIdx.x;
+  const uint32_t j = tl.y;
   if (i >= n) return;
   const size_t idx = (size_t)j * n + i;
   uint8_t res = share_precheck(s_status[idx], present == nullptr || present[idx] || i == me, i < n_keys,
@@ -475,11 +489,13 @@ __global__ void __launch_bounds__(64, 1) k_verify_shares3(const g1a* __restrict_
                                                        const line_block_d* __restrict__ lines,
                                                        const uint8_t* __restrict__ ct_ok, uint32_t n,
                                                        uint8_t* __restrict__ valid, uint32_t me,
-                                                       uint8_t* __restrict__ ct_valid) {
+                                                       uint8_t* __restrict__ ct_valid,
+                                                       const uint2* __restrict__ tiles) {
   const int lane = (int)(threadIdx.x & 63);
   const grp3 g = grp3_of_lane();
-  const uint32_t i = blockIdx.x * G3_PER_WAVE + (uint32_t)(lane / G3);
-  const uint32_t j = blockIdx.y;
+  const uint2 tl = share_tile(tiles);
+  const uint32_t i = tl.x * G3_PER_WAVE + (uint32_t)(lane / G3);
+  const uint32_t j = tl.y;
   if (lane == 63 || i >= n) return;  // whole groups
   const size_t idx = (size_t)j * n + i;
   const uint8_t res = share_precheck(s_status[idx], present == nullptr || present[idx] || i == me, i < n_keys,
@@ -506,10 +522,12 @@ __global__ void __launch_bounds__(64, 1) k_verify_shares3(const g1a* __restrict_
 template <int STEP>
 __global__ void __launch_bounds__(64) k_fe1(uint32_t* __restrict__ gslot, uint32_t n, uint8_t* __restrict__ valid,
                                             const uint8_t* __restrict__ ct_ok, uint32_t me,
-                                            uint8_t* __restrict__ ct_valid, uint32_t force_fallback) {
+                                            uint8_t* __restrict__ ct_valid, uint32_t force_fallback,
+                                            const uint2* __restrict__ tiles) {
   __shared__ uint32_t slots[FE1_WORDS * 64];  // slot A, lane-interleaved (one wave per SIMD)
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t j = blockIdx.y;
+  const uint2 tl = share_tile(tiles);
+  const uint32_t i = tl.x * blockDim.x + threadIdx.x;
+  const uint32_t j = tl.y;
   if (i >= n) return;
   const size_t idx = (size_t)j * n + i;
   const uint8_t st = valid[idx];
@@ -546,12 +564,16 @@ __global__ void __launch_bounds__(64) k_fe1(uint32_t* __restrict__ gslot, uint32
 }
 // the four step kernels compile in three translation units (tools/build.py): each is a large kernel
 #if HBX_IN_TU(8)
-template __global__ void k_fe1<0>(uint32_t*, uint32_t, uint8_t*, const uint8_t*, uint32_t, uint8_t*, uint32_t);
-template __global__ void k_fe1<5>(uint32_t*, uint32_t, uint8_t*, const uint8_t*, uint32_t, uint8_t*, uint32_t);
+template __global__ void k_fe1<0>(uint32_t*, uint32_t, uint8_t*, const uint8_t*, uint32_t, uint8_t*, uint32_t,
+                                  const uint2*);
+template __global__ void k_fe1<5>(uint32_t*, uint32_t, uint8_t*, const uint8_t*, uint32_t, uint8_t*, uint32_t,
+                                  const uint2*);
 #elif HBX_IN_TU(9)
-template __global__ void k_fe1<1>(uint32_t*, uint32_t, uint8_t*, const uint8_t*, uint32_t, uint8_t*, uint32_t);
+template __global__ void k_fe1<1>(uint32_t*, uint32_t, uint8_t*, const uint8_t*, uint32_t, uint8_t*, uint32_t,
+                                  const uint2*);
 #else
-template __global__ void k_fe1<3>(uint32_t*, uint32_t, uint8_t*, const uint8_t*, uint32_t, uint8_t*, uint32_t);
+template __global__ void k_fe1<3>(uint32_t*, uint32_t, uint8_t*, const uint8_t*, uint32_t, uint8_t*, uint32_t,
+                                  const uint2*);
 #endif
 #endif
 
@@ -568,14 +590,16 @@ __global__ void __launch_bounds__(64) k_verify_shares2(const g1a* __restrict__ S
                                                        const line_block_d* __restrict__ lines,
                                                        const uint8_t* __restrict__ ct_ok, uint32_t n,
                                                        uint8_t* __restrict__ valid, uint32_t me,
-                                                       uint8_t* __restrict__ ct_valid, uint32_t* __restrict__ gslot) {
+                                                       uint8_t* __restrict__ ct_valid, uint32_t* __restrict__ gslot,
+                                                       const uint2* __restrict__ tiles) {
   // per lane: the Miller loop's scratch, then the final exponentiation's slots A (words 0..77)
   // and B (78..155); slots G1 (t^3, then d) and G2 (b) in global memory
   __shared__ uint32_t region[LDS2_DWORDS * 64];
   const int lane = (int)(threadIdx.x & 63);
   const bool l1 = (lane & 1) != 0;
-  const uint32_t i = blockIdx.x * 32 + (uint32_t)(lane >> 1);
-  const uint32_t j = blockIdx.y;
+  const uint2 tl = share_tile(tiles);
+  const uint32_t i = tl.x * 32 + (uint32_t)(lane >> 1);
+  const uint32_t j = tl.y;
   if (i >= n) return;  // whole pairs
   const size_t idx = (size_t)j * n + i;
   const uint8_t res = share_precheck(s_status[idx], present == nullptr || present[idx] || i == me, i < n_keys,
@@ -871,7 +895,8 @@ __global__ void __launch_bounds__(COMBINE_THREADS) k_combine(const uint8_t* __re
                                                              const g1jd* __restrict__ tabs,
                                                              const uint8_t* __restrict__ tab_ok, uint32_t cap,
                                                              uint32_t tab_me, uint32_t form,
-                                                             uint32_t* __restrict__ slow) {
+                                                             uint32_t* __restrict__ slow,
+                                                             const uint32_t* __restrict__ cols) {
   __shared__ uint16_t idx[COMBINE_MAX_T];
   __shared__ int wcnt[COMBINE_THREADS / 64];
   __shared__ fr xm[COMBINE_LDS_T];  // Montgomery x_k = idx_k + 1 (t <= COMBINE_LDS_T)
@@ -879,7 +904,7 @@ __global__ void __launch_bounds__(COMBINE_THREADS) k_combine(const uint8_t* __re
   __shared__ fr tp[COMBINE_LDS_T];  // its product tree
   __shared__ g1j red[COMBINE_THREADS];
   __shared__ uint32_t slow_cnt;  // terms of this proposer without tables (slow[j])
-  const uint32_t j = blockIdx.x;
+  const uint32_t j = cols ? cols[blockIdx.x] : blockIdx.x;  // hbx_combine_decrypt_cols_d: block -> cols[b]
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   if (tid == 0) slow_cnt = 0;
   // the first t valid senders in index order (BTreeMap order, honey_badger.rs:328-340): a
@@ -1019,11 +1044,12 @@ __global__ void __launch_bounds__(64, 1) k_combine_q(const uint8_t* __restrict__
                                                      uint32_t n, uint32_t t, const uint8_t* __restrict__ ct_valid,
                                                      uint32_t* __restrict__ keys, int32_t* __restrict__ status,
                                                      int digest, g1j* __restrict__ partial,
-                                                     uint32_t* __restrict__ done, uint32_t* __restrict__ slow) {
+                                                     uint32_t* __restrict__ done, uint32_t* __restrict__ slow,
+                                                     const uint32_t* __restrict__ cols) {
   __shared__ uint16_t idx[COMBINE_LDS_T];
   __shared__ fr xm[COMBINE_LDS_T];
   __shared__ uint32_t lk[COMBQ_TERMS / 2][8];
-  const uint32_t j = blockIdx.y, b = blockIdx.x, nb = gridDim.x;
+  const uint32_t j = cols ? cols[blockIdx.y] : blockIdx.y, b = blockIdx.x, nb = gridDim.x;
   const int lane = threadIdx.x, s = lane & 3, qd = lane >> 2;
   // the first t valid senders in index order, 64 per step (as k_combine)
   int count = 0;
@@ -1144,8 +1170,9 @@ __global__ void __launch_bounds__(64) k_keystream_xor(const uint32_t* __restrict
                                                       const int32_t* __restrict__ status,
                                                       const uint8_t* __restrict__ v_blob,
                                                       const uint64_t* __restrict__ v_off,
-                                                      uint8_t* __restrict__ out) {
-  const uint32_t j = blockIdx.y;
+                                                      uint8_t* __restrict__ out,
+                                                      const uint32_t* __restrict__ cols) {
+  const uint32_t j = cols ? cols[blockIdx.y] : blockIdx.y;
   const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint64_t off = v_off[j];
   const uint64_t len = v_off[j + 1] - off;
@@ -1197,15 +1224,17 @@ __global__ void __launch_bounds__(64, 1) k_verify_shares6(const g1a* __restrict_
                                                           const line_block_d* __restrict__ lines,
                                                           const uint8_t* __restrict__ ct_ok, uint32_t n,
                                                           uint8_t* __restrict__ valid, uint32_t me,
-                                                          uint8_t* __restrict__ ct_valid, uint32_t pk_col) {
+                                                          uint8_t* __restrict__ ct_valid, uint32_t pk_col,
+                                                          const uint2* __restrict__ tiles) {
   const int lane = (int)(threadIdx.x & 63);
   if (lane >= 6 * G6_PER_WAVE) return;
   grp3 g;
   g.gl = lane % 3;
   g.base = lane - g.gl;
   const bool second = ((lane / 3) & 1) != 0;
-  const uint32_t i = blockIdx.x * G6_PER_WAVE + (uint32_t)(lane / 6);
-  const uint32_t j = blockIdx.y;
+  const uint2 tl = share_tile(tiles);
+  const uint32_t i = tl.x * G6_PER_WAVE + (uint32_t)(lane / 6);
+  const uint32_t j = tl.y;
   if (i >= n) return;  // whole groups
   const size_t idx = (size_t)j * n + i;
   const uint8_t res = share_precheck(s_status[idx], present == nullptr || present[idx] || i == me, i < n_keys,
@@ -1848,6 +1877,62 @@ __global__ void __launch_bounds__(256) k_gate_by_ct(uint8_t* __restrict__ valid,
   const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= (size_t)n * p) return;
   if (ct_valid[k / n] != HBX_CT_VALID && valid[k] <= HBX_SHARE_VALID) valid[k] = HBX_SHARE_SKIPPED_CT;
+}
+
+// hbx_add_dec_shares_d, decode: one lane per item (x = proposer column j, y = sender i), the same
+// decode as k_decompress_shares, into the candidate matrix at (j, i); the item's position is set in
+// `mask`, the present mask of the add's tile launch.  An item of a sender >= n touches nothing.
+__global__ void __launch_bounds__(256) k_add_decode(const uint8_t* __restrict__ shares, const uint2* __restrict__ items,
+                                                    uint32_t count, uint32_t n, g1a* __restrict__ S_c,
+                                                    int32_t* __restrict__ status_c, uint8_t* __restrict__ mask) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= count) return;
+  const uint2 it = items[k];
+  if (it.y >= n) return;
+  const size_t idx = (size_t)it.x * n + it.y;
+  g1a p;
+  int32_t st = g1_decompress_d(shares + (size_t)k * 48, p);
+  if (st == HBX_PT_OK && !g1_is_torsion_free_d(p)) st = HBX_PT_NOT_IN_SUBGROUP;
+  status_c[idx] = st;
+  S_c[idx] = p;
+  mask[idx] = 1;
+}
+
+// hbx_add_dec_shares_d, merge: the candidate's verdict, gated by the ciphertext's as k_gate_by_ct
+// does, is the item's status.  A VALID entry stays when the candidate is not VALID (the reference
+// returns the fault before `insert`, honey_badger.rs:198-201); otherwise the entry takes the
+// candidate's status, and its point where it decoded (`insert` replaces, :205-210).  The candidate
+// matrix is apart from the epoch's, so a kept entry was never displaced.  Clears the item's mask byte.
+__global__ void __launch_bounds__(256) k_add_merge(const uint2* __restrict__ items, uint32_t count, uint32_t n,
+                                                   const g1a* __restrict__ S_c, const int32_t* __restrict__ status_c,
+                                                   const uint8_t* __restrict__ valid_c, uint8_t* __restrict__ mask,
+                                                   const uint8_t* __restrict__ ct_valid, g1a* __restrict__ S,
+                                                   int32_t* __restrict__ s_status, uint8_t* __restrict__ valid,
+                                                   uint8_t* __restrict__ d_status) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= count) return;
+  const uint2 it = items[k];
+  if (it.y >= n) {
+    if (d_status) d_status[k] = HBX_SHARE_UNKNOWN_SENDER;
+    return;
+  }
+  const size_t idx = (size_t)it.x * n + it.y;
+  uint8_t v = valid_c[idx];
+  if (ct_valid[it.x] != HBX_CT_VALID && v <= HBX_SHARE_VALID) v = HBX_SHARE_SKIPPED_CT;
+  mask[idx] = 0;
+  if (d_status) d_status[k] = v;
+  if (valid[idx] == HBX_SHARE_VALID && v != HBX_SHARE_VALID) return;
+  const int32_t st = status_c[idx];
+  valid[idx] = v;
+  s_status[idx] = st;
+  if (st == HBX_PT_OK || st == HBX_PT_INFINITY) S[idx] = S_c[idx];
+}
+
+// hbx_combine_decrypt_cols_d: the listed proposers' combine statuses into the caller's array
+__global__ void __launch_bounds__(64) k_scatter_cols(const int32_t* __restrict__ status, const uint32_t* __restrict__ cols,
+                                                     uint32_t ncols, int32_t* __restrict__ out) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < ncols) out[cols[k]] = status[cols[k]];
 }
 #endif
 

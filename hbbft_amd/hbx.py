@@ -110,6 +110,11 @@ EXPORTS = (
     "hbx_get_ct_check_used",
     "hbx_verify_sigs_keyed",
     "hbx_sign_msgs",
+    "hbx_add_dec_shares_d",
+    "hbx_add_dec_shares",
+    "hbx_combine_decrypt_cols_d",
+    "hbx_combine_decrypt_cols",
+    "hbx_get_verify_tiles_used",
 )
 
 DIGEST_SHA256 = 0
@@ -276,6 +281,16 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.hbx_verify_sigs_keyed.argtypes = [P, u8p, u32, ctypes.POINTER(ctypes.c_uint32), u8p, u64p, u8p, u32, u8p,
                                               i32p]
         lib.hbx_sign_msgs.argtypes = [P, u8p, u8p, u64p, u32, u8p]
+    # incremental share verification: absent from a library built before it (tools/bench_incremental.py
+    # --lib times such a build through the masked matrix call)
+    if hasattr(lib, "hbx_add_dec_shares_d"):
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        lib.hbx_add_dec_shares_d.argtypes = [P, P, u32p, u32p, u32, u32, P, P]
+        lib.hbx_add_dec_shares.argtypes = [P, u8p, u32p, u32p, u32, u32, u8p]
+        lib.hbx_combine_decrypt_cols_d.argtypes = [P, u32, u32p, u32, P, P, P]
+        lib.hbx_combine_decrypt_cols.argtypes = [P, u32, u32p, u32, u8p, i32p]
+        lib.hbx_get_verify_tiles_used.argtypes = [P]
+        lib.hbx_get_verify_tiles_used.restype = u32
     _lib = lib
     return lib
 
@@ -500,6 +515,70 @@ class Context:
         for j in range(p):
             res.append(out[int(off[j]):int(off[j + 1])].tobytes() if st[j] == HBX_OK else None)
         return res, st
+
+    @staticmethod
+    def _add_items(what: str, proposer, sender, count: int):
+        """The (proposer, sender) index arrays of an add as contiguous uint32[count]."""
+        out = []
+        for name, a in (("proposer", proposer), ("sender", sender)):
+            a = np.asarray(a)
+            if a.ndim != 1 or a.shape[0] != count:
+                raise ValueError(f"{what}: {name} must have one entry per share ({count}), not shape {a.shape}")
+            if a.size and (a.dtype.kind not in "iu" or int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+                raise ValueError(f"{what}: {name} must hold node / column indices (uint32)")
+            out.append(np.ascontiguousarray(a, dtype=np.uint32))
+        return out
+
+    def add_dec_shares(self, shares48, proposer, sender, n: int) -> np.ndarray:
+        """hbx_add_dec_shares: the shares that arrived since the last call, verified and merged into
+        the epoch's matrix.  shares48 uint8[count, 48], proposer (column j < p) and sender (node
+        index) one entry each -> HBX_SHARE_* uint8[count]."""
+        shares48 = np.ascontiguousarray(shares48, dtype=np.uint8)
+        if shares48.ndim != 2 or shares48.shape[1] != 48:
+            raise ValueError(f"add_dec_shares: shares48 must be uint8[count, 48], not shape {shares48.shape}")
+        count = shares48.shape[0]
+        prop, snd = self._add_items("add_dec_shares", proposer, sender, count)
+        if n <= 0:
+            raise ValueError("add_dec_shares: n must be the number of nodes")
+        out = np.zeros(count, dtype=np.uint8)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        self._check(self.lib.hbx_add_dec_shares(
+            self.h, _u8(shares48) if count else None, prop.ctypes.data_as(u32p) if count else None,
+            snd.ctypes.data_as(u32p) if count else None, count, n, _u8(out) if count else None))
+        return out
+
+    def combine_decrypt_cols(self, t: int, cols, out=None, status=None):
+        """hbx_combine_decrypt_cols: threshold decryption of the listed proposer columns only ->
+        ({column: plaintext bytes or None}, {column: status}).  `out` (uint8[sum |V_j|]) and `status`
+        (int32[p]), if given, are the caller's buffers: only the listed proposers' ranges and entries
+        of them are written."""
+        cols = np.asarray(cols)
+        if cols.ndim != 1 or (cols.size and (cols.dtype.kind not in "iu" or int(cols.min()) < 0)):
+            raise ValueError("combine_decrypt_cols: cols must be a list of proposer columns")
+        off = self._v_off
+        if off is None:  # prepared through the device API: the caller's offsets tensor
+            off = self._d_off.detach().cpu().numpy().astype(np.uint64)
+        p = len(off) - 1
+        if cols.size and int(cols.max()) >= p:
+            raise ValueError(f"combine_decrypt_cols: column {int(cols.max())} of {p} prepared ciphertexts")
+        if len(set(cols.tolist())) != cols.size:
+            raise ValueError("combine_decrypt_cols: a column is listed twice")
+        cols = np.ascontiguousarray(cols, dtype=np.uint32)
+        out = np.zeros(max(int(off[-1]), 1), dtype=np.uint8) if out is None else out
+        st = np.zeros(p, dtype=np.int32) if status is None else status
+        if out.dtype != np.uint8 or out.size < max(int(off[-1]), 1) or not out.flags.c_contiguous or \
+                st.dtype != np.int32 or st.shape != (p,) or not st.flags.c_contiguous:
+            raise ValueError(f"combine_decrypt_cols: out must be uint8[>= {int(off[-1])}] and status int32[{p}]")
+        if cols.size:
+            self._check(self.lib.hbx_combine_decrypt_cols(
+                self.h, t, cols.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), cols.size, _u8(out),
+                st.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        plains = {int(j): (out[int(off[j]):int(off[j + 1])].tobytes() if st[j] == HBX_OK else None) for j in cols}
+        return plains, {int(j): int(st[j]) for j in cols}
+
+    def verify_tiles_used(self) -> int:
+        """Check blocks of the last share-check launch (hbx_get_verify_tiles_used)."""
+        return int(self.lib.hbx_get_verify_tiles_used(self.h))
 
     def share_status(self, p: int, n: int) -> np.ndarray:
         """HBX_SHARE_* byte of every share of the last verification -> uint8[p, n]."""
@@ -1134,3 +1213,29 @@ class Context:
             self.h, d_u.data_ptr(), d_v.data_ptr(), d_off.data_ptr(), d_w.data_ptr(), p, max_v_len,
             d_shares.data_ptr(), opt(d_present), n, t, opt(d_valid), opt(d_ct_valid), d_out.data_ptr(),
             opt(d_status), self._stream(stream)))
+
+    def add_dec_shares_d(self, d_shares48, proposer, sender, n: int, d_status=None, stream=None):
+        """hbx_add_dec_shares_d: d_shares48 a device uint8[count, 48] tensor (None with no items),
+        proposer / sender host index arrays, d_status an optional device uint8[count]."""
+        count = 0 if d_shares48 is None else int(d_shares48.shape[0])
+        if d_shares48 is not None and (d_shares48.dim() != 2 or d_shares48.shape[1] != 48):
+            raise ValueError(f"add_dec_shares_d: d_shares48 must be uint8[count, 48], not shape {tuple(d_shares48.shape)}")
+        prop, snd = self._add_items("add_dec_shares_d", proposer, sender, count)
+        if d_status is not None and d_status.numel() != count:
+            raise ValueError(f"add_dec_shares_d: d_status must have one byte per share ({count})")
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        self._check(self.lib.hbx_add_dec_shares_d(
+            self.h, d_shares48.data_ptr() if count else None, prop.ctypes.data_as(u32p) if count else None,
+            snd.ctypes.data_as(u32p) if count else None, count, n,
+            None if d_status is None or not count else d_status.data_ptr(), self._stream(stream)))
+
+    def combine_decrypt_cols_d(self, t: int, cols, d_out, d_status=None, stream=None):
+        """hbx_combine_decrypt_cols_d: cols a host list of proposer columns; d_out / d_status as for
+        combine_decrypt_d (only the listed proposers' ranges and entries are written)."""
+        cols = np.asarray(cols)
+        if cols.ndim != 1 or (cols.size and (cols.dtype.kind not in "iu" or int(cols.min()) < 0)):
+            raise ValueError("combine_decrypt_cols_d: cols must be a list of proposer columns")
+        cols = np.ascontiguousarray(cols, dtype=np.uint32)
+        self._check(self.lib.hbx_combine_decrypt_cols_d(
+            self.h, t, cols.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if cols.size else None, cols.size,
+            d_out.data_ptr(), None if d_status is None else d_status.data_ptr(), self._stream(stream)))

@@ -211,3 +211,228 @@ class EpochReplay:
                     continue
                 out[pid] = plains[j]
         return out
+
+
+@dataclass
+class FlushResult:
+    """What one ``EpochSession.flush`` added: FaultLog entries and errors in the reference's order,
+    and the proposers decrypted since the last flush."""
+    faults: List[Tuple[int, str]] = field(default_factory=list)
+    errors: List[Tuple[int, str]] = field(default_factory=list)
+    decrypted: Dict[int, bytes] = field(default_factory=dict)  # proposer -> contribution
+    decrypt_errors: List[int] = field(default_factory=list)  # proposers whose decrypt failed (:345)
+
+
+class EpochSession:
+    """One node-epoch of the decryption sub-path, driven by messages as they arrive.
+
+    ``EpochReplay`` decides a finished epoch in one pass; a node that is running the epoch calls
+    ``handle(event)`` per message and ``flush()`` whenever it wants the engine brought up to date
+    (after every message, or after a burst).  The results are the reference's, whatever the flush
+    schedule:
+
+    * before the CommonSubset output, shares are held on the host (``insert``: the last decodable
+      message of a (proposer, sender) pair is the one the node holds, honey_badger.rs:205-210);
+    * at the CommonSubset output: one ``prepare_ciphertexts`` and one matrix verification of the held
+      shares -- the reference's own batch point, ``verify_pending_decryption_shares`` (:422-444).  A
+      pair whose last message does not decode falls back to its earlier ones through adds;
+    * after it: one ``add_dec_shares`` per flush (``handle_decryption_share_message``, :186-217), and
+      one more per further message of the same pair within the flush;
+    * within a flush the messages are replayed in arrival order over the status bytes, which gives
+      the fault order, ``UnknownSender``, the ``all()`` short-circuit of ``try_output_batch`` and the
+      decrypt errors as the reference emits them, and reports nothing after the batch is output;
+    * the proposers that cross the threshold in a flush are decrypted by one
+      ``combine_decrypt_cols`` (``try_decrypt_proposer_contribution``, :315-349).
+
+    ``ctx`` must hold the era's key shares; ``sk_me`` is this node's 32-byte secret key share
+    (own-share mode).  Message model: ``oracle/honey_badger.py``'s, as for ``EpochReplay``."""
+
+    def __init__(self, ctx, n: int, me: int, sk_me: bytes):
+        self.ctx = ctx
+        self.n = n
+        self.f = (n - 1) // 3
+        self.t = self.f + 1
+        self.me = me
+        self.sk_me = bytes(sk_me)
+        self.faults: List[Tuple[int, str]] = []
+        self.errors: List[Tuple[int, str]] = []
+        self.decrypted: Dict[int, bytes] = {}
+        self.decrypt_errors: List[int] = []
+        self.batch: Optional[Dict[int, bytes]] = None
+        self.done = False
+        self.ct_status: Dict[int, int] = {}
+        self.share_status: List[Optional[int]] = []  # per handled event: HBX_SHARE_* if it was verified
+        self._queue: List[tuple] = []
+        self._held: Dict[Tuple[int, int], List[Tuple[int, bytes]]] = {}  # before the ACS: pair -> messages
+        self._props: List[int] = []
+        self._col: Dict[int, int] = {}
+        self._valid_cts: Optional[List[int]] = None
+        self._received: Dict[int, set] = {}  # proposer -> senders whose share the node holds
+        self._reached: set = set()  # proposers past the threshold (decrypted or failed to)
+        self._to_decrypt: List[int] = []
+
+    def handle(self, event):
+        """Queues one message; nothing reaches the engine before ``flush``."""
+        if event[0] not in ("share", "acs"):
+            raise ValueError(event[0])
+        self._queue.append(event)
+
+    # ------------------------------------------------------------------------------------------
+    def _try_output(self):
+        if self.done or self._valid_cts is None:
+            return
+        for pid in self._valid_cts:  # all(): stops at the first proposer still short of shares
+            if pid in self._reached:
+                continue
+            if len(self._received.get(pid, ())) <= self.f:
+                return
+            self._reached.add(pid)
+            self._to_decrypt.append(pid)
+        self.done = True
+
+    def _share_event(self, k: int, ev, status: Dict[int, int]):
+        """handle_decryption_share_message over the engine's status byte of message k."""
+        _, sender, pid, _ = ev
+        if sender >= self.n:
+            self.errors.append((sender, UNKNOWN_SENDER))
+            return
+        st = status.get(k)
+        if pid not in self._col or st == SHARE_UNDECODABLE:
+            return  # no ciphertext of that proposer this epoch / serde rejects the message
+        if pid in self._valid_cts and st == SHARE_INVALID:
+            self.faults.append((sender, UNVERIFIED_DECRYPTION_SHARE_SENDER))
+            return
+        self._received.setdefault(pid, set()).add(sender)
+        self._try_output()
+
+    def _add_layers(self, items: List[Tuple[int, int, int, bytes]], status: Dict[int, int]):
+        """items (event index, column, sender, share48) in arrival order -> one add per layer, layer
+        L holding the L-th message of every pair."""
+        layers: List[List[Tuple[int, int, int, bytes]]] = []
+        seen: Dict[Tuple[int, int], int] = {}
+        for it in items:
+            L = seen.get((it[1], it[2]), 0)
+            seen[(it[1], it[2])] = L + 1
+            if L == len(layers):
+                layers.append([])
+            layers[L].append(it)
+        for layer in layers:
+            shares = np.frombuffer(b"".join(bytes(it[3]) for it in layer), dtype=np.uint8).reshape(len(layer), 48)
+            st = self.ctx.add_dec_shares(shares, np.array([it[1] for it in layer], dtype=np.uint32),
+                                         np.array([it[2] for it in layer], dtype=np.uint32), self.n)
+            for it, s in zip(layer, st):
+                status[it[0]] = int(s)
+                self.share_status[it[0]] = int(s)
+
+    def _acs_event(self, cs_output):
+        """send_decryption_shares: prepare, one matrix verification of the held shares, the faults."""
+        if self._valid_cts is not None:
+            raise ValueError("one CommonSubset output per epoch")
+        self._props = sorted(cs_output)
+        self._col = {pid: j for j, pid in enumerate(self._props)}
+        p, n = len(self._props), self.n
+        self.ctx.set_own_share(self.me, self.sk_me)
+        self.ctx.prepare_ciphertexts([cs_output[pid] for pid in self._props])
+        ct = self.ctx.ct_status(p)
+        self.ct_status = {pid: int(ct[j]) for j, pid in enumerate(self._props)}
+        held = {(self._col[pid], sender): msgs for (pid, sender), msgs in self._held.items() if pid in self._col}
+        shares = np.zeros((p, n, 48), dtype=np.uint8)
+        present = np.zeros((p, n), dtype=bool)
+        for (j, i), msgs in held.items():
+            shares[j, i] = np.frombuffer(bytes(msgs[-1][1]), dtype=np.uint8)
+            present[j, i] = True
+        self.ctx.verify_dec_shares(shares, present)
+        st = self.ctx.share_status(p, n)
+        pair_st: Dict[Tuple[int, int], int] = {}
+        for (j, i), msgs in held.items():
+            pair_st[(j, i)] = int(st[j, i])
+            self.share_status[msgs[-1][0]] = int(st[j, i])
+        # a pair whose last message serde rejects still holds its last decodable one
+        depth = 2
+        while True:
+            back = [(msgs[-depth][0], j, i, msgs[-depth][1]) for (j, i), msgs in held.items()
+                    if pair_st[(j, i)] == SHARE_UNDECODABLE and len(msgs) >= depth]
+            if not back:
+                break
+            got: Dict[int, int] = {}
+            self._add_layers(back, got)
+            for k, j, i, _ in back:
+                pair_st[(j, i)] = got[k]
+            depth += 1
+        self._held = {}
+        self._valid_cts = []
+        for j, pid in enumerate(self._props):
+            if self.ct_status[pid] == CT_UNDECODABLE:
+                self.faults.append((pid, INVALID_CIPHERTEXT))
+                continue
+            if self.ct_status[pid] == CT_INVALID:
+                self.faults.append((pid, SHARE_DECRYPTION_FAILED))
+                continue
+            assert self.ct_status[pid] == CT_VALID
+            got_from = set()
+            for sender in sorted(i for (jj, i) in pair_st if jj == j):
+                if pair_st[(j, sender)] == SHARE_UNDECODABLE:
+                    continue
+                if pair_st[(j, sender)] == SHARE_INVALID:
+                    self.faults.append((sender, UNVERIFIED_DECRYPTION_SHARE_SENDER))
+                    continue
+                got_from.add(sender)
+            got_from.add(self.me)  # our own share
+            self._received[pid] = got_from
+            self._valid_cts.append(pid)
+        self._try_output()
+
+    def flush(self) -> FlushResult:
+        """Brings the engine up to date with the queued messages."""
+        f0, e0, d0 = len(self.faults), len(self.errors), len(self.decrypt_errors)
+        events, self._queue = self._queue, []
+        k0 = len(self.share_status)
+        self.share_status.extend([None] * len(events))
+        pos = 0
+        while pos < len(events) and not self.done:
+            if self._valid_cts is None:
+                ev = events[pos]
+                if ev[0] == "acs":
+                    self._acs_event(ev[1])
+                else:
+                    _, sender, pid, share48 = ev
+                    if sender >= self.n:
+                        self.errors.append((sender, UNKNOWN_SENDER))
+                    elif sender == self.me:
+                        raise ValueError("a node does not receive its own DecryptionShare messages")
+                    else:
+                        self._held.setdefault((pid, sender), []).append((k0 + pos, bytes(share48)))
+                pos += 1
+                continue
+            # after the CommonSubset output: the rest of the flush through adds, then in arrival order
+            rest = events[pos:]
+            items = []
+            for q, ev in enumerate(rest):
+                if ev[0] == "acs":
+                    raise ValueError("one CommonSubset output per epoch")
+                _, sender, pid, share48 = ev
+                if sender == self.me:
+                    raise ValueError("a node does not receive its own DecryptionShare messages")
+                if sender < self.n and pid in self._col:
+                    items.append((k0 + pos + q, self._col[pid], sender, bytes(share48)))
+            status: Dict[int, int] = {}
+            self._add_layers(items, status)
+            for q, ev in enumerate(rest):
+                if self.done:
+                    break  # messages of a past epoch are ignored (:68-76)
+                self._share_event(k0 + pos + q, ev, status)
+            pos = len(events)
+        new: Dict[int, bytes] = {}
+        if self._to_decrypt:
+            pids, self._to_decrypt = self._to_decrypt, []
+            plains, st = self.ctx.combine_decrypt_cols(self.t, [self._col[pid] for pid in pids])
+            for pid in pids:
+                j = self._col[pid]
+                if st[j] != 0:
+                    self.decrypt_errors.append(pid)  # the reference only logs it (:345)
+                else:
+                    new[pid] = plains[j]
+            self.decrypted.update(new)
+        if self.done and self.batch is None:
+            self.batch = dict(self.decrypted)
+        return FlushResult(self.faults[f0:], self.errors[e0:], new, self.decrypt_errors[d0:])

@@ -330,6 +330,62 @@ int hbx_decrypt_epoch_d(hbx_ctx* ctx, const uint8_t* d_u_comp, const uint8_t* d_
                         uint8_t* d_out_blob, int32_t* d_status, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Incremental share verification: the shares that arrive after the epoch's ciphertexts are
+ * prepared, verified on arrival and merged into the epoch's p x n matrix.
+ * Replaces: HoneyBadger::handle_decryption_share_message (src/honey_badger/honey_badger.rs:186-217,
+ * the check at :198) for a node that is running the epoch, where hbx_verify_dec_shares[_d] decides
+ * a finished one.  Item k is the 48 bytes shares48[k] for position (proposer[k] = column j < p,
+ * sender[k] = node index i); the launch covers the tiles of the check kernels that the items touch,
+ * not n * p, and the lanes per check follow the touched-tile count (hbx_set_verify_lanes overrides;
+ * hbx_get_verify_lanes_used, hbx_debug_force_fallback, hbx_debug_force_degenerate and
+ * hbx_get_fallback_lanes mean for an add what they mean for a matrix verification).
+ *
+ * The matrix: after hbx_verify_dec_shares[_d] or hbx_decrypt_epoch_d the add continues from that
+ * call's matrix (n must be its n).  On a context whose latest prepare has not been followed by a
+ * share verification of the same p, the add first behaves exactly as hbx_verify_dec_shares_d with
+ * every present byte 0 and this n (own-share mode enters and checks this node's shares, a deferred
+ * Ciphertext::verify is decided, the batched mode runs if a seed is set); count == 0 is allowed
+ * (pointers may then be NULL) and only does that.  A prepare voids the matrix.
+ *
+ * status[k] is the HBX_SHARE_* byte hbx_verify_dec_shares_d writes for the same bytes at (j, i) of
+ * the same epoch; sender[k] >= n gives HBX_SHARE_UNKNOWN_SENDER and touches no position.  The items
+ * always run the per-share checks: a batch seed is neither used nor advanced by them.
+ * Merge: an entry that is HBX_SHARE_VALID keeps its point and status when the item is not VALID
+ * (the reference returns the fault before `insert`, :198-201); in every other case the entry takes
+ * the item's status, and its point where it decoded (`insert` replaces, :205-210).  No other entry
+ * changes, so delivering every share of an epoch once, in any partition into calls, leaves the
+ * matrix, hbx_get_share_status, hbx_get_ct_status and the combine as one matrix call does.  The
+ * precomputed combine tables of a fused call are void after an add.
+ *
+ * HBX_E_INVALID_ARG before anything is launched: proposer[k] >= p; the same (proposer, sender)
+ * twice in one call (the second message of a pair goes into a later call); n different from the
+ * matrix's; in own-share mode, sender[k] == me.  HBX_E_NO_KEYS / HBX_E_NO_CIPHERTEXTS as for the
+ * matrix call.  The host index arrays are consumed before the call returns.  The _d form is
+ * stream-ordered and does not synchronise (d_status may be NULL); the host form blocks.
+ * ------------------------------------------------------------------------------------------- */
+int hbx_add_dec_shares_d(hbx_ctx* ctx, const uint8_t* d_shares48 /* [count][48] */,
+                         const uint32_t* proposer /* HOST [count]: column j < p */,
+                         const uint32_t* sender /* HOST [count]: node index */, uint32_t count, uint32_t n,
+                         uint8_t* d_status /* [count], may be NULL */, void* stream);
+int hbx_add_dec_shares(hbx_ctx* ctx, const uint8_t* shares48, const uint32_t* proposer, const uint32_t* sender,
+                       uint32_t count, uint32_t n, uint8_t* status);
+/* Threshold decryption of the listed proposers only: try_decrypt_proposer_contribution
+ * (src/honey_badger/honey_badger.rs:315-349) for the proposers that crossed the threshold.  Reads
+ * what hbx_combine_decrypt_d reads (the first t VALID entries in index order at call time) and
+ * writes only status[cols[k]] and the v_off ranges of the listed proposers that decrypted: no other
+ * byte of either output changes.  cols (HOST, consumed before the call returns): cols[k] >= p or a
+ * repeated column is HBX_E_INVALID_ARG; ncols == 0 is a no-op that returns HBX_OK.  The lanes per
+ * Lagrange term are chosen as by hbx_set_combine_lanes with ncols in the place of p. */
+int hbx_combine_decrypt_cols_d(hbx_ctx* ctx, uint32_t t, const uint32_t* cols /* HOST [ncols] */, uint32_t ncols,
+                               uint8_t* d_out_blob, int32_t* d_status /* [p] */, void* stream);
+int hbx_combine_decrypt_cols(hbx_ctx* ctx, uint32_t t, const uint32_t* cols, uint32_t ncols, uint8_t* out_blob,
+                             int32_t* status);
+/* Check blocks (64-thread tiles) of the last share-check launch: grid.x * grid.y for a matrix
+ * verification, the tile-list length for an add; 0 before any.  Diagnostics: no reference
+ * counterpart. */
+uint32_t hbx_get_verify_tiles_used(const hbx_ctx* ctx);
+
+/* ---------------------------------------------------------------------------------------------
  * Producer side.  Scalars are canonical Fr values as
  * 32-byte big-endian strings (< r; anything else is HBX_E_INVALID_ARG).
  *
