@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -26,27 +27,35 @@ using namespace hbx;
 
 namespace {
 
-// one wave per SIMD: a one-lane-per-check launch with fewer waves leaves SIMDs idle, and the
-// three-lane kernel finishes it sooner (MI355X: 256 CUs x 4 SIMDs)
-constexpr int VERIFY_FILL_WAVES = 1024;
+// one wave per SIMD: a one-lane-per-check launch with fewer waves leaves SIMDs idle (addplan.hpp)
+constexpr size_t FILL_WAVES = hbx_addplan::FILL_WAVES;
 // the combine's precomputed tables: what k_prepare_lines' table lanes build (prepare_impl)
 constexpr uint32_t COMB_FORM = 1;
+
+// Ownership rule: every device allocation is a dbuf, every pinned one a pinbuf, every event a
+// dev_event or the timing pool's, and each frees what it holds in its destructor: a context's by
+// `delete`, a per-call temporary's at the end of its scope.  No list names a buffer to free it.
+// live_buffers: the device and pinned allocations this process holds (hbx_debug_live_buffers).
+std::atomic<uint64_t> live_buffers{0};
 
 struct dbuf {
   void* p = nullptr;
   size_t cap = 0;
+  dbuf() = default;
+  dbuf(const dbuf&) = delete;
+  dbuf& operator=(const dbuf&) = delete;
+  ~dbuf() { release(); }
   bool ensure(size_t bytes) {
     if (bytes <= cap && p) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
+    release();
     if (bytes == 0) bytes = 16;
     if (hipMalloc(&p, bytes) != hipSuccess) return false;
+    live_buffers++;
     cap = bytes;
     return true;
   }
   void release() {
-    if (p) (void)hipFree(p);
+    if (p && hipFree(p) == hipSuccess) live_buffers--;
     p = nullptr;
     cap = 0;
   }
@@ -56,13 +65,82 @@ struct dbuf {
   }
 };
 
+// Pinned host memory; grows with half as much again, so a run of slightly longer calls reallocates once.
+struct pinbuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  pinbuf() = default;
+  pinbuf(const pinbuf&) = delete;
+  pinbuf& operator=(const pinbuf&) = delete;
+  ~pinbuf() { release(); }
+  bool ensure(size_t bytes) {
+    if (bytes <= cap) return true;
+    release();
+    const size_t want = bytes + bytes / 2 + 4096;
+    if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) return false;
+    live_buffers++;
+    cap = want;
+    return true;
+  }
+  void release() {
+    if (p && hipHostFree(p) == hipSuccess) live_buffers--;
+    p = nullptr;
+    cap = 0;
+  }
+};
+
+// An ordering event (no timing), created on first use; `recorded`: there is something to wait for.
+struct dev_event {
+  hipEvent_t e = nullptr;
+  bool recorded = false;
+  dev_event() = default;
+  dev_event(const dev_event&) = delete;
+  dev_event& operator=(const dev_event&) = delete;
+  ~dev_event() {
+    if (e) (void)hipEventDestroy(e);
+  }
+  hipError_t create() { return e ? hipSuccess : hipEventCreateWithFlags(&e, hipEventDisableTiming); }
+};
+
+// opt-in kernel timing: event pairs per timed kernel (hbx_set_timing / hbx_kernel_time)
+struct timing_state {
+  bool on = false;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> tev[HBX_K_COUNT];
+  std::vector<hipEvent_t> pool;
+  timing_state() = default;
+  timing_state(const timing_state&) = delete;
+  timing_state& operator=(const timing_state&) = delete;
+  ~timing_state() {
+    reset();
+    for (hipEvent_t e : pool) (void)hipEventDestroy(e);
+  }
+  hipEvent_t get() {
+    if (!pool.empty()) {
+      hipEvent_t e = pool.back();
+      pool.pop_back();
+      return e;
+    }
+    hipEvent_t e = nullptr;
+    return hipEventCreate(&e) == hipSuccess ? e : nullptr;
+  }
+  void reset() {
+    for (auto& v : tev) {
+      for (auto& pr : v) {
+        pool.push_back(pr.first);
+        pool.push_back(pr.second);
+      }
+      v.clear();
+    }
+  }
+};
+
 }  // namespace
 
 struct hbx_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   bool coin_h_ready = false;  // coin_H (the true hash_g2 of the prepared nonces) computed
-  hipEvent_t coin_ready_ev = nullptr;  // end of hbx_prepare_nonces' work: later coin calls on any stream wait on it
+  dev_event coin_ready_ev;  // end of hbx_prepare_nonces' work: later coin calls on any stream wait on it
   std::string err = "ok";
   int digest = DIGEST_SHA256;         // hbx_set_digest: threshold_crypto's DIGEST
   int merkle = 0;                     // hbx_set_merkle_digest: HBX_MERKLE_*
@@ -143,10 +221,8 @@ struct hbx_ctx {
   // and uploaded to rg_dev in one async copy; rg_ev marks the end of that copy, the only thing a
   // later call waits for on the host (before it rewrites the staging)
   dbuf rg_dev;
-  void* rg_pin = nullptr;
-  size_t rg_pin_cap = 0;
-  hipEvent_t rg_ev = nullptr;
-  bool rg_ev_recorded = false;
+  pinbuf rg_pin;
+  dev_event rg_ev;
   // common coin state: nonces' hash_g2 points and lines, signature shares, combined signatures
   uint32_t coin_I = 0, coin_n = 0;
   dbuf coin_blob, coin_off, coin_H, coin_Hp, coin_lines, coin_scratch, coin_sk, coin_sig96, coin_sig, coin_sig_st, coin_present,
@@ -165,38 +241,23 @@ struct hbx_ctx {
   dbuf bv_commit48, bv_C, bv_cst, bv_rows, bv_rows48, bv_pst, bv_ackp, bv_acky, bv_vals, bv_out;
   // SyncKeyGen SecretKey::decrypt (hbx_sk_decrypt): the key's limbs, plaintexts, HBX_CT_* per ciphertext
   dbuf kg_sk, kg_out, kg_st;
-  // opt-in kernel timing: event pairs per timed kernel (hbx_set_timing / hbx_kernel_time)
-  bool timing = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> tev[HBX_K_COUNT];
-  std::vector<hipEvent_t> ev_pool;
+  timing_state timing;
   // ordering of this context's work across streams: every entry point waits on `ev_last` before
   // enqueuing on its stream and records it after (stream_scope), so a host call on `stream`
   // after a _d call on the caller's stream (or on NULL, which does not order against the
   // non-blocking `stream`) sees that call's results; readouts wait on this event only, not on
   // the whole device (other contexts' epochs in flight keep running)
-  hipEvent_t ev_last = nullptr;
-  bool ev_recorded = false;
+  dev_event ev_last;
+  // a new set of prepared ciphertexts (or none): S / valid of an earlier verify belong to other
+  // ciphertexts, the combine's tables to other shares
+  void invalidate_epoch() {
+    ct_known = false;
+    n_shares = 0;
+    verified_p = 0;
+    tab_ready = false;
+  }
 };
 
-static hipEvent_t ev_get(hbx_ctx* c) {
-  if (!c->ev_pool.empty()) {
-    hipEvent_t e = c->ev_pool.back();
-    c->ev_pool.pop_back();
-    return e;
-  }
-  hipEvent_t e = nullptr;
-  if (hipEventCreate(&e) != hipSuccess) return nullptr;
-  return e;
-}
-static void timing_reset(hbx_ctx* c) {
-  for (auto& v : c->tev) {
-    for (auto& pr : v) {
-      c->ev_pool.push_back(pr.first);
-      c->ev_pool.push_back(pr.second);
-    }
-    v.clear();
-  }
-}
 // Records a start event before and a stop event after one kernel launch on stream s.
 struct timed {
   hbx_ctx* c;
@@ -204,14 +265,14 @@ struct timed {
   hipStream_t s;
   hipEvent_t e0 = nullptr;
   timed(hbx_ctx* c_, int id_, hipStream_t s_) : c(c_), id(id_), s(s_) {
-    if (c->timing && (e0 = ev_get(c))) (void)hipEventRecord(e0, s);
+    if (c->timing.on && (e0 = c->timing.get())) (void)hipEventRecord(e0, s);
   }
   ~timed() {
     if (!e0) return;
-    hipEvent_t e1 = ev_get(c);
+    hipEvent_t e1 = c->timing.get();
     if (!e1) return;
     (void)hipEventRecord(e1, s);
-    c->tev[id].emplace_back(e0, e1);
+    c->timing.tev[id].emplace_back(e0, e1);
   }
 };
 
@@ -230,13 +291,14 @@ static int fail(hbx_ctx* c, int code, const char* fmt, ...) {
     hipError_t e_ = (expr);                                                                    \
     if (e_ != hipSuccess) return fail(ctx, HBX_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
+#define HBX_DEVICE(c) HIPCHK(c, hipSetDevice(c->device))
 
 // _d API: the caller's stream; NULL is the HIP null stream (a framework's default stream), so the
 // enqueued work is ordered with the caller's own work on it.  The stream first waits for this
 // context's previous work on any stream (ev_last).
 static hipStream_t pick(hbx_ctx* c, void* s) {
   hipStream_t st = static_cast<hipStream_t>(s);
-  if (c && c->ev_recorded) (void)hipStreamWaitEvent(st, c->ev_last, 0);
+  if (c && c->ev_last.recorded) (void)hipStreamWaitEvent(st, c->ev_last.e, 0);
   return st;
 }
 // Records ev_last on the entry point's stream when it returns (on every return path).
@@ -244,13 +306,19 @@ struct stream_scope {
   hbx_ctx* c;
   hipStream_t s;
   ~stream_scope() {
-    if (c && c->ev_last && hipEventRecord(c->ev_last, s) == hipSuccess) c->ev_recorded = true;
+    if (c && c->ev_last.e && hipEventRecord(c->ev_last.e, s) == hipSuccess) c->ev_last.recorded = true;
   }
 };
+// The prologue of an entry point, after its argument checks: this context's device, `s` = the
+// call's stream ordered after the context's earlier work, ev_last recorded on it at every return.
+#define HBX_ENTER(c, on_stream)                          \
+  HBX_DEVICE(c);                                         \
+  [[maybe_unused]] hipStream_t s = pick(c, on_stream);   \
+  stream_scope ss_ { c, s }
 // Host-side wait for everything this context has enqueued (its own stream and callers' streams).
 static hipError_t quiesce(hbx_ctx* c) {
-  if (c->ev_recorded) {
-    const hipError_t e = hipEventSynchronize(c->ev_last);
+  if (c->ev_last.recorded) {
+    const hipError_t e = hipEventSynchronize(c->ev_last.e);
     if (e != hipSuccess) return e;
   }
   return hipStreamSynchronize(c->stream);
@@ -587,7 +655,7 @@ int hbx_ctx_create(int device, hbx_ctx** out) {
     delete c;
     return HBX_E_DEVICE;
   }
-  if (hipEventCreateWithFlags(&c->ev_last, hipEventDisableTiming) != hipSuccess) {
+  if (c->ev_last.create() != hipSuccess) {
     (void)hipStreamDestroy(c->stream);
     delete c;
     return HBX_E_DEVICE;
@@ -600,32 +668,9 @@ int hbx_ctx_destroy(hbx_ctx* c) {
   if (!c) return HBX_E_INVALID_ARG;
   (void)hipSetDevice(c->device);
   (void)quiesce(c);
-  timing_reset(c);
-  for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-  c->ev_pool.clear();
-  dbuf* bufs[] = {&c->comb_partial, &c->comb_done, &c->pk,       &c->pk_m,       &c->pk64,       &c->g1tab,      &c->pk_status,  &c->pk_comp,     &c->U,         &c->G2pts, &c->Hj,
-                  &c->lines,    &c->scratch,    &c->ct_ok,       &c->ct_valid,  &c->v_blob_own,
-                  &c->v_off_own, &c->u_comp_own, &c->w_comp_own, &c->S,         &c->valid,
-                  &c->S_status, &c->fallback, &c->gslot,
-                  &c->shares_own, &c->present_own, &c->keys,     &c->status,    &c->out_own,
-                  &c->gf_log,   &c->gf_exp,     &c->rs_enc,      &c->rs_enc_job, &c->rs_enc_coef, &c->rs_enc_ptab, &c->rs_ptab_d, &c->rs_ptab_p,
-                  &c->rs_jobs_d, &c->rs_jobs_p, &c->rs_coef_d,   &c->rs_coef_p, &c->leaf_hash, &c->leaf_slots, &c->val_digest, &c->roots,
-                  &c->coin_blob, &c->coin_off,  &c->coin_H, &c->coin_Hp,      &c->coin_lines, &c->coin_scratch, &c->coin_sk,
-                  &c->coin_sig96, &c->coin_sig, &c->coin_sig_st, &c->coin_present, &c->coin_valid, &c->coin_comb,
-                  &c->coin_comb_st, &c->coin_mpk_comp, &c->coin_mpk, &c->coin_mpk_st, &c->coin_ok, &c->coin_par,
-                  &c->coin_out96, &c->dec_st, &c->own_sk, &c->own_S, &c->own_part, &c->lines_d, &c->lines_u, &c->line_degen,
-                  &c->vs_pk, &c->vs_lines_d, &c->coin_lines_d, &c->vs_blob, &c->vs_off, &c->vs_H, &c->vs_lines, &c->vs_scratch, &c->vs_sig96,
-                  &c->vs_sig, &c->vs_sig_st, &c->vs_status, &c->fe1slot, &c->fb_lanes, &c->fb_coin, &c->fb_ct, &c->fb_sigs, &c->vk_pk48, &c->vk_pk, &c->vk_pkst, &c->vk_idx, &c->vk_gslot, &c->vk_sk, &c->hs[0], &c->hs[1], &c->hs[2], &c->hs[3], &c->hs[4], &c->hs[5], &c->coin_use, &c->bv_commit48, &c->bv_C, &c->bv_cst, &c->bv_rows,
-                  &c->bv_rows48, &c->bv_pst, &c->bv_ackp, &c->bv_acky, &c->bv_vals, &c->bv_out,
-                  &c->kg_sk, &c->kg_out, &c->kg_st, &c->b_seed, &c->b_AJ, &c->b_T, &c->b_C, &c->b_Asum, &c->b_A, &c->b_B,
-                  &c->b_cls0, &c->b_cand, &c->b_pass, &c->b_zero, &c->b_cls, &c->b_ctok, &c->b_stats, &c->rg_dev, &c->comb_tab, &c->comb_tab_ok, &c->comb_slow};
-  for (dbuf* b : bufs) b->release();
-  if (c->rg_pin) (void)hipHostFree(c->rg_pin);
-  if (c->rg_ev) (void)hipEventDestroy(c->rg_ev);
-  (void)hipEventDestroy(c->ev_last);
-  if (c->coin_ready_ev) (void)hipEventDestroy(c->coin_ready_ev);
-  (void)hipStreamDestroy(c->stream);
-  delete c;
+  const hipStream_t stream = c->stream;
+  delete c;  // every buffer and event the context holds frees itself
+  (void)hipStreamDestroy(stream);
   return HBX_OK;
 }
 
@@ -634,10 +679,7 @@ int hbx_set_digest(hbx_ctx* c, int variant) {
     return fail(c, HBX_E_INVALID_ARG, "hbx_set_digest: unknown variant %d", variant);
   c->digest = variant == HBX_DIGEST_SHA3_256 ? DIGEST_SHA3_256 : DIGEST_SHA256;
   c->p_ct = 0;  // hashes prepared under the other digest are void
-  c->ct_known = false;
-  c->n_shares = 0;
-  c->verified_p = 0;
-  c->tab_ready = false;
+  c->invalidate_epoch();
   c->coin_I = 0;
   c->coin_n = 0;
   return HBX_OK;
@@ -676,7 +718,7 @@ int hbx_debug_force_degenerate(hbx_ctx* c, uint32_t every) {
 int64_t hbx_get_fallback_lanes(hbx_ctx* c) {
   if (!c) return HBX_E_INVALID_ARG;
   if (!c->fb_last) return 0;
-  HIPCHK(c, hipSetDevice(c->device));
+  HBX_DEVICE(c);
   HIPCHK(c, quiesce(c));
   uint32_t v = 0;
   HIPCHK(c, hipMemcpy(&v, c->fb_last->p, 4, hipMemcpyDeviceToHost));
@@ -693,7 +735,7 @@ int hbx_debug_set_combine_margin(hbx_ctx* c, int32_t margin) {
 int64_t hbx_get_combine_slow_terms(hbx_ctx* c) {
   if (!c) return HBX_E_INVALID_ARG;
   if (!c->comb_slow.p || c->comb_slow_p == 0) return 0;
-  HIPCHK(c, hipSetDevice(c->device));
+  HBX_DEVICE(c);
   HIPCHK(c, quiesce(c));
   std::vector<uint32_t> v(c->comb_slow_p);
   HIPCHK(c, hipMemcpy(v.data(), c->comb_slow.p, v.size() * 4, hipMemcpyDeviceToHost));
@@ -709,7 +751,7 @@ static bool combine_quads(const hbx_ctx* c, uint32_t t, uint32_t p) {
   const uint32_t nb = (2 * t + COMBQ_TERMS - 1) / COMBQ_TERMS;
   return c->combine_lanes == 4 ? nb <= 16
          : c->combine_lanes == 1 ? false
-                                 : nb <= 16 && (size_t)nb * p <= (size_t)VERIFY_FILL_WAVES;
+                                 : nb <= 16 && (size_t)nb * p <= FILL_WAVES;
 }
 
 // Senders per proposer whose window tables the fused epoch call precomputes (0: none): the first
@@ -723,7 +765,7 @@ static uint32_t combine_tab_cap(const hbx_ctx* c, uint32_t n, uint32_t t, uint32
 
 int hbx_set_batch_verify(hbx_ctx* c, const uint8_t* seed32) {
   if (!c) return HBX_E_INVALID_ARG;
-  HIPCHK(c, hipSetDevice(c->device));
+  HBX_DEVICE(c);
   HIPCHK(c, quiesce(c));  // a verification enqueued earlier may still read the old seed
   c->batch_call = 0;
   c->batch_on = false;
@@ -738,7 +780,7 @@ int hbx_get_batch_stats(hbx_ctx* c, uint32_t* cols_batched, uint32_t* cols_fallb
   if (!c) return HBX_E_INVALID_ARG;
   uint32_t v[3] = {0, 0, 0};
   if (c->batch_last_p) {
-    HIPCHK(c, hipSetDevice(c->device));
+    HBX_DEVICE(c);
     HIPCHK(c, quiesce(c));
     HIPCHK(c, hipMemcpy(v, c->b_stats.p, 12, hipMemcpyDeviceToHost));
   }
@@ -753,7 +795,7 @@ int hbx_get_batch_sums(hbx_ctx* c, uint8_t* a48, size_t count) {
   if (c->batch_last_p == 0) return fail(c, HBX_E_NO_CIPHERTEXTS, "hbx_get_batch_sums: the last verification was not batched");
   if (count != c->batch_last_p)
     return fail(c, HBX_E_INVALID_ARG, "hbx_get_batch_sums: count %zu, expected %u", count, c->batch_last_p);
-  HIPCHK(c, hipSetDevice(c->device));
+  HBX_DEVICE(c);
   HIPCHK(c, quiesce(c));
   dbuf out;
   if (!out.ensure(count * 48)) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_get_batch_sums: out of device memory");
@@ -762,7 +804,6 @@ int hbx_get_batch_sums(hbx_ctx* c, uint8_t* a48, size_t count) {
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e == hipSuccess) e = hipMemcpy(a48, out.p, count * 48, hipMemcpyDeviceToHost);
-  out.release();
   if (e != hipSuccess) return fail(c, HBX_E_DEVICE, "hbx_get_batch_sums: %s", hipGetErrorString(e));
   return HBX_OK;
 }
@@ -783,7 +824,7 @@ int hbx_set_merkle_digest(hbx_ctx* c, int variant) {
 
 int hbx_set_pk_shares(hbx_ctx* c, const uint8_t* pk_comp, uint32_t n, int32_t* status) {
   if (!c || (!pk_comp && n)) return fail(c, HBX_E_INVALID_ARG, "hbx_set_pk_shares: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
+  HBX_DEVICE(c);
   // era change: nothing enqueued earlier (on any stream) may still read the old keys, and every
   // state derived from them is void -- the own share (its pk_me check was against the old keys)
   // and the current epoch's prepared ciphertexts / verified shares
@@ -792,10 +833,7 @@ int hbx_set_pk_shares(hbx_ctx* c, const uint8_t* pk_comp, uint32_t n, int32_t* s
   c->own_me = UINT32_MAX;
   c->own_ready = false;
   c->p_ct = 0;
-  c->ct_known = false;
-  c->n_shares = 0;
-  c->verified_p = 0;
-  c->tab_ready = false;
+  c->invalidate_epoch();
   c->coin_n = 0;
   if (!c->pk.ensure((size_t)n * sizeof(g1a)) || !c->pk_m.ensure((size_t)n * sizeof(g1a)) ||
       !c->pk64.ensure((size_t)n * sizeof(g1a)) || !c->pk_status.ensure((size_t)n * 4) || !c->pk_comp.ensure((size_t)n * 48))
@@ -900,9 +938,7 @@ static int prepare_impl(hbx_ctx* c, const uint8_t* d_u_comp, const uint8_t* d_v_
                         void* stream, const uint8_t* early_shares, uint32_t early_n, uint32_t tab_cap = 0) {
   if (!c || p == 0 || !d_u_comp || !d_v_off || !d_w_comp)
     return fail(c, HBX_E_INVALID_ARG, "hbx_prepare_ciphertexts_d: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, stream);
   if (!c->U.ensure((size_t)p * sizeof(g1a)) || !c->G2pts.ensure((size_t)2 * p * sizeof(g2a)) || !c->Hj.ensure((size_t)p * sizeof(g2j)) ||
       !c->lines.ensure((size_t)p * sizeof(line_block)) || !c->lines_d.ensure((size_t)p * sizeof(line_block_d)) ||
       !c->lines_u.ensure((size_t)p * sizeof(line_block_d)) || !c->line_degen.ensure(p) ||
@@ -959,10 +995,8 @@ static int prepare_impl(hbx_ctx* c, const uint8_t* d_u_comp, const uint8_t* d_v_
   }
   HIPCHK(c, hipGetLastError());
   c->p_ct = p;
-  c->ct_known = false;
-  c->n_shares = 0;  // S / valid of an earlier verify belong to other ciphertexts
-  c->verified_p = 0;
-  c->tab_ready = tab_cap != 0;  // tables of an earlier fused call belong to other shares
+  c->invalidate_epoch();
+  c->tab_ready = tab_cap != 0;  // this call's tables, if it made any
   c->tab_cap = tab_cap;
   c->tab_me = me_early;
   c->tab_n = early_n;
@@ -993,8 +1027,7 @@ int hbx_prepare_ciphertexts(hbx_ctx* c, const uint8_t* u_comp, const uint8_t* v_
                             const uint8_t* w_comp, uint32_t p, uint8_t* ct_valid_bits) {
   if (!c || p == 0 || !u_comp || !v_off || !w_comp)
     return fail(c, HBX_E_INVALID_ARG, "hbx_prepare_ciphertexts: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
-  stream_scope ss_{c, pick(c, c->stream)};
+  HBX_ENTER(c, c->stream);
   const uint64_t vbytes = v_off[p];
   uint64_t maxv = 0;
   for (uint32_t j = 0; j < p; j++) {
@@ -1077,9 +1110,7 @@ static int verify_impl(hbx_ctx* c, const uint8_t* d_shares, const uint8_t* d_pre
   if (!c || !d_shares || n == 0 || p == 0) return fail(c, HBX_E_INVALID_ARG, "hbx_verify_dec_shares_d: bad args");
   if (c->n_keys == 0) return fail(c, HBX_E_NO_KEYS, "hbx_set_pk_shares has not been called");
   if (p != c->p_ct) return fail(c, HBX_E_NO_CIPHERTEXTS, "p=%u but %u ciphertexts prepared", p, c->p_ct);
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, stream);
   const size_t m = (size_t)n * p;
   if (!c->S.ensure(m * sizeof(g1a)) || !c->S_status.ensure(m * 4) || !c->valid.ensure(m))
     return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_verify_dec_shares_d: out of device memory");
@@ -1118,19 +1149,13 @@ static int verify_impl(hbx_ctx* c, const uint8_t* d_shares, const uint8_t* d_pre
     // below a full chip: the most lanes per check that still fit one wave per SIMD -- six, three,
     // then two (an N=256 epoch over 2 GPUs: 1,024 two-lane waves, 11.0 ms against 17.4 for the
     // three-lane check in two rounds of waves, profiles/r04w_lanes.txt)
-    const size_t waves1 = (size_t)((n + 63) / 64) * p;
-    const size_t waves2 = (size_t)((n + 31) / 32) * p;
-    const size_t waves3 = (size_t)((n + G3_PER_WAVE - 1) / G3_PER_WAVE) * p;
-    const size_t waves6 = (size_t)((n + G6_PER_WAVE - 1) / G6_PER_WAVE) * p;
-    const size_t fill = (size_t)VERIFY_FILL_WAVES;
-    const int lanes = c->verify_lanes   ? c->verify_lanes
-                      : waves1 >= fill ? 1
-                      : waves6 <= fill ? 6
-                      : waves3 <= fill ? 3
-                      : waves2 <= fill ? 2
-                                       : 3;
+    // (the ladder itself: addplan.hpp choose_lanes, over the whole matrix's tiles of each shape)
+    namespace ap = hbx_addplan;
+    auto tiles_of = [&](int shape) { return (size_t)((n + ap::SHAPE_SENDERS[shape] - 1) / ap::SHAPE_SENDERS[shape]) * p; };
+    const int lanes =
+        c->verify_lanes ? c->verify_lanes : ap::choose_lanes(tiles_of(0), tiles_of(3), tiles_of(2), tiles_of(1));
     c->lanes_used = lanes;
-    const uint32_t per = lanes == 2 ? 32u : lanes == 6 ? (uint32_t)G6_PER_WAVE : lanes == 3 ? (uint32_t)G3_PER_WAVE : 64u;
+    const uint32_t per = ap::SHAPE_SENDERS[ap::shape_of_lanes(lanes)];
     c->verify_tiles = (uint32_t)((n + per - 1) / per) * p;
     if (int rc = launch_share_checks(c, s, lanes, dim3((n + per - 1) / per, p), nullptr, c->S.as<g1a>(),
                                      c->S_status.as<int32_t>(), d_present, c->valid.as<uint8_t>(), ctok, n,
@@ -1165,8 +1190,7 @@ int hbx_verify_dec_shares_d(hbx_ctx* c, const uint8_t* d_shares, const uint8_t* 
 int hbx_verify_dec_shares(hbx_ctx* c, const uint8_t* shares, const uint8_t* present_bits, uint32_t n,
                           uint32_t p, uint8_t* valid_bits) {
   if (!c || !shares || n == 0 || p == 0) return fail(c, HBX_E_INVALID_ARG, "hbx_verify_dec_shares: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
-  stream_scope ss_{c, pick(c, c->stream)};
+  HBX_ENTER(c, c->stream);
   const size_t m = (size_t)n * p;
   if (!c->shares_own.ensure(m * 48) || (present_bits && !c->present_own.ensure(m)))
     return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_verify_dec_shares: out of device memory");
@@ -1190,9 +1214,7 @@ int hbx_verify_dec_shares(hbx_ctx* c, const uint8_t* shares, const uint8_t* pres
 
 int hbx_rs_encode_d(hbx_ctx* c, uint8_t* d_shards, uint32_t inst, uint32_t k, uint32_t m, uint32_t L, void* stream) {
   if (!c || !d_shards || inst == 0 || L == 0) return fail(c, HBX_E_INVALID_ARG, "hbx_rs_encode_d: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, stream);
   if (m == 0) return HBX_OK;  // Coding::Trivial
   int rc = rs_setup(c, k, m, s);
   if (rc) return rc;
@@ -1206,9 +1228,7 @@ int hbx_rs_reconstruct_d(hbx_ctx* c, uint8_t* d_shards, const uint8_t* d_present
                          uint32_t m, uint32_t L, int32_t* d_status, void* stream) {
   if (!c || !d_shards || !d_present || !d_status || inst == 0 || L == 0)
     return fail(c, HBX_E_INVALID_ARG, "hbx_rs_reconstruct_d: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, stream);
   int rc = rs_setup(c, k, m, s);
   if (rc) return rc;
   return rs_reconstruct(c, d_shards, d_present, inst, k, m, L, d_status, s);
@@ -1217,9 +1237,7 @@ int hbx_rs_reconstruct_d(hbx_ctx* c, uint8_t* d_shards, const uint8_t* d_present
 int hbx_merkle_roots_d(hbx_ctx* c, const uint8_t* d_shards, uint32_t inst, uint32_t n, uint32_t L, uint8_t* d_roots,
                        void* stream) {
   if (!c || !d_shards || !d_roots || inst == 0) return fail(c, HBX_E_INVALID_ARG, "hbx_merkle_roots_d: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, stream);
   return merkle_roots(c, d_shards, inst, n, L, d_roots, s);
 }
 
@@ -1230,9 +1248,7 @@ int hbx_merkle_validate_d(hbx_ctx* c, const uint8_t* d_values, uint32_t vlen, co
   if (!c || !d_values || !d_node_hash || !d_sib_hash || !d_sides || !d_depth || !d_root || !d_sender || !d_valid ||
       nproofs == 0 || vlen == 0)
     return fail(c, HBX_E_INVALID_ARG, "hbx_merkle_validate_d: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, stream);
   // long values (Echo proofs of real shards): their leaf digests first, by the leaf kernels (the
   // producer/consumer SHA-256 or the two-lane SHA3 schedule) instead of one lane per value inside
   // the path check
@@ -1262,9 +1278,7 @@ uint32_t hbx_merkle_node_count(uint32_t n) { return n ? merkle_node_count(n) : 0
 int hbx_merkle_build_d(hbx_ctx* c, const uint8_t* d_shards, uint32_t inst, uint32_t n, uint32_t L, uint8_t* d_nodes,
                        uint8_t* d_roots, void* stream) {
   if (!c || !d_shards || !d_nodes || inst == 0) return fail(c, HBX_E_INVALID_ARG, "hbx_merkle_build_d: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, stream);
   uint8_t* roots = d_roots;
   if (!roots) {
     if (!c->roots.ensure((size_t)inst * 32)) return fail(c, HBX_E_OUT_OF_MEMORY, "merkle: roots");
@@ -1279,9 +1293,7 @@ int hbx_merkle_proofs_d(hbx_ctx* c, const uint8_t* d_nodes, uint32_t n, const ui
   if (!c || !d_nodes || !d_req || !d_node_hash || !d_sib_hash || !d_sides || !d_depth || !d_root || count == 0 ||
       n == 0 || n > (uint32_t)RS_MAX_N)
     return fail(c, HBX_E_INVALID_ARG, "hbx_merkle_proofs_d: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, stream);
   hipLaunchKernelGGL(k_merkle_proofs, dim3((count + 63) / 64), dim3(64), 0, s, d_nodes, n, d_req, count,
                      d_node_hash, d_sib_hash, d_sides, d_depth, d_root);
   HIPCHK(c, hipGetLastError());
@@ -1300,9 +1312,7 @@ static int broadcast_decode(hbx_ctx* c, uint8_t* d_shards, const uint8_t* d_pres
   if ((uint64_t)k * L >= 4 && out_stride < (uint64_t)k * L - 4)
     return fail(c, HBX_E_INVALID_ARG, "hbx_broadcast_decode_d: out_stride %llu < k L - 4 = %llu",
                 (unsigned long long)out_stride, (unsigned long long)((uint64_t)k * L - 4));
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, stream);
   int rc = rs_setup(c, k, m, s);
   if (rc) return rc;
   rc = rs_reconstruct(c, d_shards, d_present, inst, k, m, L, d_status, s);
@@ -1365,28 +1375,20 @@ int hbx_broadcast_decode_leaves_d(hbx_ctx* c, uint8_t* d_shards, const uint8_t* 
 // The host descriptors of a call (rg_desc per instance, and the call's other host arrays) are
 // laid out in the context's pinned staging buffer and uploaded with one asynchronous copy on the
 // call's stream, so the caller's arrays are consumed at return and nothing waits for the device
-// -- except a later ragged call, which waits for the previous upload (not the previous kernels)
-// before it rewrites the staging, and rs_setup's one-off synchronisation per (k, m).
-static uint8_t* rg_begin(hbx_ctx* c, size_t bytes) {
-  if (c->rg_ev_recorded && hipEventSynchronize(c->rg_ev) != hipSuccess) return nullptr;
-  c->rg_ev_recorded = false;
-  if (bytes > c->rg_pin_cap) {
-    if (c->rg_pin) (void)hipHostFree(c->rg_pin);
-    c->rg_pin = nullptr;
-    c->rg_pin_cap = 0;
-    const size_t cap = bytes + bytes / 2 + 4096;
-    if (hipHostMalloc(&c->rg_pin, cap, hipHostMallocDefault) != hipSuccess) return nullptr;
-    c->rg_pin_cap = cap;
-  }
-  if (!c->rg_ev && hipEventCreateWithFlags(&c->rg_ev, hipEventDisableTiming) != hipSuccess) return nullptr;
-  if (!c->rg_dev.ensure(bytes)) return nullptr;
-  return static_cast<uint8_t*>(c->rg_pin);
+// -- except a later staged call, which waits for the previous upload (not the previous kernels)
+// before it rewrites the staging, and rs_setup's one-off synchronisation per (k, m).  The same
+// staging carries an add's items and tile list and the column combine's list.
+static uint8_t* staging_begin(hbx_ctx* c, size_t bytes) {
+  if (c->rg_ev.recorded && hipEventSynchronize(c->rg_ev.e) != hipSuccess) return nullptr;
+  c->rg_ev.recorded = false;
+  if (!c->rg_pin.ensure(bytes) || c->rg_ev.create() != hipSuccess || !c->rg_dev.ensure(bytes)) return nullptr;
+  return static_cast<uint8_t*>(c->rg_pin.p);
 }
 
-static int rg_upload(hbx_ctx* c, size_t bytes, hipStream_t s) {
-  HIPCHK(c, hipMemcpyAsync(c->rg_dev.p, c->rg_pin, bytes, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipEventRecord(c->rg_ev, s));
-  c->rg_ev_recorded = true;
+static int staging_upload(hbx_ctx* c, size_t bytes, hipStream_t s) {
+  HIPCHK(c, hipMemcpyAsync(c->rg_dev.p, c->rg_pin.p, bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipEventRecord(c->rg_ev.e, s));
+  c->rg_ev.recorded = true;
   return HBX_OK;
 }
 
@@ -1495,17 +1497,15 @@ int hbx_rs_encode_ragged_d(hbx_ctx* c, uint8_t* d_buf, uint64_t buf_bytes, const
   uint32_t max_len = 0;
   int rc = rg_check(c, "hbx_rs_encode_ragged_d", buf_bytes, off, len, pitch, inst, k + m, &max_len);
   if (rc) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, stream);
   if (m == 0) return HBX_OK;  // Coding::Trivial
   rc = rs_setup(c, k, m, s);
   if (rc) return rc;
   const size_t bytes = (size_t)inst * sizeof(rg_desc);
-  uint8_t* h = rg_begin(c, bytes);
+  uint8_t* h = staging_begin(c, bytes);
   if (!h) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_rs_encode_ragged_d: descriptor staging");
   rg_fill(reinterpret_cast<rg_desc*>(h), off, len, pitch, inst);
-  rc = rg_upload(c, bytes, s);
+  rc = staging_upload(c, bytes, s);
   if (rc) return rc;
   rs_code_rg(c, d_buf, c->rg_dev.as<rg_desc>(), max_len, k, inst, c->rs_enc_job.as<rs_job>(),
              c->rs_enc_ptab.as<gf_ptab>(), 0u, m, s);
@@ -1522,16 +1522,14 @@ int hbx_rs_reconstruct_ragged_d(hbx_ctx* c, uint8_t* d_buf, uint64_t buf_bytes, 
   uint32_t max_len = 0;
   int rc = rg_check(c, "hbx_rs_reconstruct_ragged_d", buf_bytes, off, len, pitch, inst, k + m, &max_len);
   if (rc) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, stream);
   rc = rs_setup(c, k, m, s);
   if (rc) return rc;
   const size_t bytes = (size_t)inst * sizeof(rg_desc);
-  uint8_t* h = rg_begin(c, bytes);
+  uint8_t* h = staging_begin(c, bytes);
   if (!h) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_rs_reconstruct_ragged_d: descriptor staging");
   rg_fill(reinterpret_cast<rg_desc*>(h), off, len, pitch, inst);
-  rc = rg_upload(c, bytes, s);
+  rc = staging_upload(c, bytes, s);
   if (rc) return rc;
   return rs_reconstruct_rg(c, d_buf, c->rg_dev.as<rg_desc>(), max_len, d_present, inst, k, m, d_status, s);
 }
@@ -1544,16 +1542,14 @@ int hbx_merkle_build_ragged_d(hbx_ctx* c, const uint8_t* d_buf, uint64_t buf_byt
   uint32_t max_len = 0;
   int rc = rg_check(c, "hbx_merkle_build_ragged_d", buf_bytes, off, len, pitch, inst, n, &max_len);
   if (rc) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, stream);
   if (!c->leaf_hash.ensure((size_t)inst * n * 32) || (!d_roots && !c->roots.ensure((size_t)inst * 32)))
     return fail(c, HBX_E_OUT_OF_MEMORY, "merkle: leaf hashes");
   const size_t bytes = (size_t)inst * sizeof(rg_desc);
-  uint8_t* h = rg_begin(c, bytes);
+  uint8_t* h = staging_begin(c, bytes);
   if (!h) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_merkle_build_ragged_d: descriptor staging");
   rg_fill(reinterpret_cast<rg_desc*>(h), off, len, pitch, inst);
-  rc = rg_upload(c, bytes, s);
+  rc = staging_upload(c, bytes, s);
   if (rc) return rc;
   return merkle_tree_rg(c, d_buf, c->rg_dev.as<rg_desc>(), inst, n, nullptr, 0, true,
                         d_roots ? d_roots : c->roots.as<uint8_t>(), d_nodes, s);
@@ -1572,9 +1568,7 @@ int hbx_merkle_validate_ragged_d(hbx_ctx* c, const uint8_t* d_values, uint64_t v
   if (val_off[nproofs] > values_bytes)
     return fail(c, HBX_E_INVALID_ARG, "hbx_merkle_validate_ragged_d: val_off ends at %llu, past the %llu value bytes",
                 (unsigned long long)val_off[nproofs], (unsigned long long)values_bytes);
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, stream);
   // long values (more than 256 bytes: Echo proofs of real shards) get their leaf digests from the
   // leaf kernels, in blocks of one length each: sorted by (length, index), every run of a length is
   // cut into blocks of B lanes.  The digests land at the proof's own index, so neither the order
@@ -1596,7 +1590,7 @@ int hbx_merkle_validate_ragged_d(hbx_ctx* c, const uint8_t* d_values, uint64_t v
   const size_t nblk = blk_len.size();
   const size_t o_len = (size_t)(nproofs + 1) * 8, o_idx = o_len + ((nblk * 4 + 7) & ~(size_t)7),
                bytes = o_idx + nblk * B * 4;
-  uint8_t* h = rg_begin(c, bytes);
+  uint8_t* h = staging_begin(c, bytes);
   if (!h || (nblk && !c->val_digest.ensure((size_t)nproofs * 32)))
     return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_merkle_validate_ragged_d: out of memory");
   memcpy(h, val_off, o_len);
@@ -1604,7 +1598,7 @@ int hbx_merkle_validate_ragged_d(hbx_ctx* c, const uint8_t* d_values, uint64_t v
     memcpy(h + o_len, blk_len.data(), nblk * 4);
     memcpy(h + o_idx, blk_idx.data(), nblk * B * 4);
   }
-  int rc = rg_upload(c, bytes, s);
+  int rc = staging_upload(c, bytes, s);
   if (rc) return rc;
   const uint8_t* dv = c->rg_dev.as<uint8_t>();
   const uint64_t* d_off = reinterpret_cast<const uint64_t*>(dv);
@@ -1654,20 +1648,18 @@ int hbx_broadcast_decode_ragged_d(hbx_ctx* c, uint8_t* d_buf, uint64_t buf_bytes
   std::sort(rng.begin(), rng.end());
   for (size_t r = 1; r < rng.size(); r++)
     if (rng[r].first < rng[r - 1].second) return fail(c, HBX_E_INVALID_ARG, "%s: output ranges overlap", fn);
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, stream);
   rc = rs_setup(c, k, m, s);
   if (rc) return rc;
   if (!c->roots.ensure((size_t)inst * 32) || !c->leaf_hash.ensure((size_t)inst * n * 32) ||
       !c->leaf_slots.ensure((size_t)inst * (m ? m : 1) * 2))
     return fail(c, HBX_E_OUT_OF_MEMORY, "%s: out of device memory", fn);
   const size_t o_out = (size_t)inst * sizeof(rg_desc), bytes = o_out + (size_t)inst * 8;
-  uint8_t* h = rg_begin(c, bytes);
+  uint8_t* h = staging_begin(c, bytes);
   if (!h) return fail(c, HBX_E_OUT_OF_MEMORY, "%s: descriptor staging", fn);
   rg_fill(reinterpret_cast<rg_desc*>(h), off, len, pitch, inst);
   memcpy(h + o_out, out_off, (size_t)inst * 8);
-  rc = rg_upload(c, bytes, s);
+  rc = staging_upload(c, bytes, s);
   if (rc) return rc;
   const rg_desc* d_desc = c->rg_dev.as<rg_desc>();
   rc = rs_reconstruct_rg(c, d_buf, d_desc, max_len, d_present, inst, k, m, d_status, s);
@@ -1710,8 +1702,7 @@ static uint8_t* stage(hbx_ctx* c, int slot, size_t bytes) {
 int hbx_rs_encode(hbx_ctx* c, uint8_t* shards, uint32_t inst, uint32_t k, uint32_t m, uint32_t L) {
   if (!c || !shards || inst == 0 || L == 0) return fail(c, HBX_E_INVALID_ARG, "hbx_rs_encode: bad args");
   if (m == 0) return HBX_OK;  // Coding::Trivial
-  HIPCHK(c, hipSetDevice(c->device));
-  stream_scope ss_{c, pick(c, c->stream)};
+  HBX_ENTER(c, c->stream);
   const size_t row = (size_t)(k + m) * L;
   HBX_STAGE(d, 0, row * inst, "hbx_rs_encode");
   // the k data shards of every instance in, the m parity shards out (one strided copy each way)
@@ -1728,8 +1719,7 @@ int hbx_rs_reconstruct(hbx_ctx* c, uint8_t* shards, const uint8_t* present, uint
                        uint32_t L, int32_t* status) {
   if (!c || !shards || !present || !status || inst == 0 || L == 0)
     return fail(c, HBX_E_INVALID_ARG, "hbx_rs_reconstruct: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
-  stream_scope ss_{c, pick(c, c->stream)};
+  HBX_ENTER(c, c->stream);
   const size_t n = (size_t)k + m, all = n * L * inst;
   HBX_STAGE(d, 0, all, "hbx_rs_reconstruct");
   HBX_STAGE(dp, 1, n * inst, "hbx_rs_reconstruct");
@@ -1746,8 +1736,7 @@ int hbx_rs_reconstruct(hbx_ctx* c, uint8_t* shards, const uint8_t* present, uint
 
 int hbx_merkle_roots(hbx_ctx* c, const uint8_t* shards, uint32_t inst, uint32_t n, uint32_t L, uint8_t* roots) {
   if (!c || !shards || !roots || inst == 0) return fail(c, HBX_E_INVALID_ARG, "hbx_merkle_roots: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
-  stream_scope ss_{c, pick(c, c->stream)};
+  HBX_ENTER(c, c->stream);
   const size_t all = (size_t)n * L * inst;
   HBX_STAGE(d, 0, all, "hbx_merkle_roots");
   HBX_STAGE(dr, 1, (size_t)inst * 32, "hbx_merkle_roots");
@@ -1762,8 +1751,7 @@ int hbx_merkle_roots(hbx_ctx* c, const uint8_t* shards, uint32_t inst, uint32_t 
 int hbx_merkle_build(hbx_ctx* c, const uint8_t* shards, uint32_t inst, uint32_t n, uint32_t L, uint8_t* nodes,
                      uint8_t* roots) {
   if (!c || !shards || !nodes || inst == 0 || n == 0) return fail(c, HBX_E_INVALID_ARG, "hbx_merkle_build: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
-  stream_scope ss_{c, pick(c, c->stream)};
+  HBX_ENTER(c, c->stream);
   const size_t all = (size_t)n * L * inst, nb = (size_t)inst * merkle_node_count(n) * 32;
   HBX_STAGE(d, 0, all, "hbx_merkle_build");
   HBX_STAGE(dn, 1, nb, "hbx_merkle_build");
@@ -1786,8 +1774,7 @@ int hbx_merkle_proofs(hbx_ctx* c, const uint8_t* nodes, uint32_t inst, uint32_t 
     if (req[2 * q] >= inst || req[2 * q + 1] >= n)
       return fail(c, HBX_E_INVALID_ARG, "hbx_merkle_proofs: request %u names leaf %u of instance %u (inst %u, n %u)",
                   q, req[2 * q + 1], req[2 * q], inst, n);
-  HIPCHK(c, hipSetDevice(c->device));
-  stream_scope ss_{c, pick(c, c->stream)};
+  HBX_ENTER(c, c->stream);
   const size_t nb = (size_t)inst * merkle_node_count(n) * 32;
   HBX_STAGE(dn, 0, nb, "hbx_merkle_proofs");
   HBX_STAGE(dq, 1, (size_t)count * 8, "hbx_merkle_proofs");
@@ -1818,8 +1805,7 @@ int hbx_merkle_validate(hbx_ctx* c, const uint8_t* values, uint32_t vlen, const 
   if (!c || !values || !node_hash || !sib_hash || !sides || !depth || !root || !sender || !valid || nproofs == 0 ||
       vlen == 0)
     return fail(c, HBX_E_INVALID_ARG, "hbx_merkle_validate: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
-  stream_scope ss_{c, pick(c, c->stream)};
+  HBX_ENTER(c, c->stream);
   const size_t P = nproofs;
   HBX_STAGE(dv, 0, P * vlen, "hbx_merkle_validate");
   HBX_STAGE(dh, 1, P * 17 * 32, "hbx_merkle_validate");
@@ -1848,8 +1834,7 @@ static int broadcast_decode_host(hbx_ctx* c, uint8_t* shards, const uint8_t* pre
                                  const char* what) {
   if (!c || !shards || !present || !root_expect || !out || !out_len || !status || inst == 0 || L == 0)
     return fail(c, HBX_E_INVALID_ARG, "%s: bad args", what);
-  HIPCHK(c, hipSetDevice(c->device));
-  stream_scope ss_{c, pick(c, c->stream)};
+  HBX_ENTER(c, c->stream);
   const size_t n = (size_t)k + m, all = n * L * inst;
   HBX_STAGE(d, 0, all, what);
   HBX_STAGE(dp, 1, n * inst, what);
@@ -1913,9 +1898,7 @@ int hbx_prepare_nonces(hbx_ctx* c, const uint8_t* nonce_blob, const uint64_t* no
     if (nonce_off[j + 1] < nonce_off[j]) return fail(c, HBX_E_INVALID_ARG, "nonce_off not monotone");
   const uint64_t total = nonce_off[count];
   if (total && !nonce_blob) return fail(c, HBX_E_INVALID_ARG, "hbx_prepare_nonces: null blob");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, c->stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, c->stream);
   if (!c->coin_blob.ensure(total ? total : 16) || !c->coin_off.ensure((size_t)(count + 1) * 8) ||
       !c->coin_H.ensure((size_t)count * sizeof(g2a)) || !c->coin_Hp.ensure((size_t)count * sizeof(g2a)) ||
       !c->coin_lines.ensure((size_t)count * MILLER_LINES * sizeof(line_pre)) ||
@@ -1947,8 +1930,8 @@ int hbx_prepare_nonces(hbx_ctx* c, const uint8_t* nonce_blob, const uint64_t* no
     HIPCHK(c, hipMemcpyAsync(h96, c->coin_out96.p, (size_t)count * 96, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
   }
-  if (!c->coin_ready_ev) HIPCHK(c, hipEventCreateWithFlags(&c->coin_ready_ev, hipEventDisableTiming));
-  HIPCHK(c, hipEventRecord(c->coin_ready_ev, s));
+  HIPCHK(c, c->coin_ready_ev.create());
+  HIPCHK(c, hipEventRecord(c->coin_ready_ev.e, s));
   c->coin_I = count;
   return HBX_OK;
 }
@@ -1957,9 +1940,7 @@ int hbx_sign(hbx_ctx* c, const uint8_t* sk32, uint32_t n, uint8_t* sig96) {
   if (!c || !sk32 || !sig96 || n == 0) return fail(c, HBX_E_INVALID_ARG, "hbx_sign: bad args");
   if (c->coin_I == 0) return fail(c, HBX_E_NO_CIPHERTEXTS, "hbx_prepare_nonces has not been called");
   if (!scalars_canonical(sk32, n)) return fail(c, HBX_E_INVALID_ARG, "hbx_sign: scalar >= r");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, c->stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, c->stream);
   const size_t m = (size_t)n * c->coin_I;
   if (!c->coin_sk.ensure((size_t)n * 32) || !c->coin_sig96.ensure(m * 96))
     return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_sign: out of device memory");
@@ -1980,7 +1961,7 @@ static int verify_sig_impl(hbx_ctx* c, const uint8_t* d_sig96, const uint8_t* d_
   const size_t m = (size_t)n * count;
   if (!c->coin_sig.ensure(m * sizeof(g2a)) || !c->coin_sig_st.ensure(m * 4) || !c->coin_valid.ensure(m))
     return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_verify_sig_shares: out of device memory");
-  if (c->coin_ready_ev) HIPCHK(c, hipStreamWaitEvent(s, c->coin_ready_ev, 0));  // the nonces' hashes are in
+  if (c->coin_ready_ev.e) HIPCHK(c, hipStreamWaitEvent(s, c->coin_ready_ev.e, 0));  // the nonces' hashes are in
   {
     timed t_(c, HBX_K_DECODE_SIGS, s);
     // curve membership only: the share checks test G2 membership on their Miller loop's [|x|] sigma
@@ -1993,7 +1974,7 @@ static int verify_sig_impl(hbx_ctx* c, const uint8_t* d_sig96, const uint8_t* d_
   // (hbx_set_verify_lanes 2); one lane otherwise
   const size_t waves1 = (size_t)((n + 63) / 64) * count;
   const int lanes = c->verify_lanes == 1 || c->verify_lanes == 2 ? c->verify_lanes
-                    : waves1 < (size_t)VERIFY_FILL_WAVES ? 2 : 1;
+                    : waves1 < FILL_WAVES ? 2 : 1;
   c->coin_lanes_used = lanes;
   if (!c->coin_lines_ready) {
     // H''s prepared lines (wave-uniform loads): the one-lane kernel's mixed loop, and since round 6
@@ -2010,8 +1991,8 @@ static int verify_sig_impl(hbx_ctx* c, const uint8_t* d_sig96, const uint8_t* d_
     c->coin_lines_ready = true;
     // the lines are built on this call's stream: move the prepare event past them, so a later
     // one-lane check on another stream (which waits on coin_ready_ev) is ordered after the build
-    if (!c->coin_ready_ev) HIPCHK(c, hipEventCreateWithFlags(&c->coin_ready_ev, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(c->coin_ready_ev, s));
+    HIPCHK(c, c->coin_ready_ev.create());
+    HIPCHK(c, hipEventRecord(c->coin_ready_ev.e, s));
   }
   {
     timed t_(c, HBX_K_VERIFY_SIG, s);
@@ -2061,9 +2042,7 @@ int hbx_verify_sig_shares(hbx_ctx* c, const uint8_t* sig96, const uint8_t* prese
                           uint8_t* valid_bits) {
   if (!c || !sig96 || n == 0 || count == 0) return fail(c, HBX_E_INVALID_ARG, "hbx_verify_sig_shares: bad args");
   if (int rc = verify_sig_check(c, n, count)) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, c->stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, c->stream);
   const size_t m = (size_t)n * count;
   if (!c->coin_sig96.ensure(m * 96) || (present_bits && !c->coin_present.ensure(m)))
     return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_verify_sig_shares: out of device memory");
@@ -2088,9 +2067,7 @@ int hbx_verify_sig_shares_d(hbx_ctx* c, const uint8_t* d_sig96, const uint8_t* d
                             uint8_t* d_status, void* stream) {
   if (!c || !d_sig96 || n == 0 || count == 0) return fail(c, HBX_E_INVALID_ARG, "hbx_verify_sig_shares_d: bad args");
   if (int rc = verify_sig_check(c, n, count)) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, stream);
   if (int rc = verify_sig_impl(c, d_sig96, d_present, n, count, s)) return rc;
   if (d_status) HIPCHK(c, hipMemcpyAsync(d_status, c->coin_valid.p, (size_t)n * count, hipMemcpyDeviceToDevice, s));
   return HBX_OK;
@@ -2106,9 +2083,7 @@ int hbx_verify_sigs(hbx_ctx* c, const uint8_t* pk48, const uint8_t* msg_blob, co
     if (msg_off[i + 1] < msg_off[i]) return fail(c, HBX_E_INVALID_ARG, "hbx_verify_sigs: msg_off not monotone");
   const uint64_t total = msg_off[count];
   if (total && !msg_blob) return fail(c, HBX_E_INVALID_ARG, "hbx_verify_sigs: null blob");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, c->stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, c->stream);
   if (!c->vs_pk.ensure((size_t)count * 48) || !c->vs_blob.ensure(total ? total : 16) ||
       !c->vs_off.ensure((size_t)(count + 1) * 8) || !c->vs_H.ensure((size_t)count * sizeof(g2a)) ||
       !c->vs_lines.ensure((size_t)count * MILLER_LINES * sizeof(line_pre)) ||
@@ -2174,9 +2149,7 @@ int hbx_verify_sigs_keyed(hbx_ctx* c, const uint8_t* pk48, uint32_t nkeys, const
     return fail(c, HBX_E_INVALID_ARG, "hbx_verify_sigs_keyed: bad args");
   uint64_t total = 0;
   if (int rc = msgs_check(c, "hbx_verify_sigs_keyed", msg_blob, msg_off, count, &total)) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, c->stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, c->stream);
   // every buffer is sized here, before the first pass: the per-item state for one chunk only
   const size_t cap = std::min(VERIFY_SIGS_CHUNK, count);
   const uint64_t base = msg_off[0], end = msg_off[count];
@@ -2249,9 +2222,7 @@ int hbx_sign_msgs(hbx_ctx* c, const uint8_t* sk32, const uint8_t* msg_blob, cons
   static const uint8_t zero32[32] = {0};
   if (!scalars_canonical(sk32, 1) || memcmp(sk32, zero32, 32) == 0)
     return fail(c, HBX_E_INVALID_ARG, "hbx_sign_msgs: secret key not in [1, r)");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, c->stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, c->stream);
   const size_t cap = std::min(VERIFY_SIGS_CHUNK, count);
   const uint64_t base = msg_off[0], end = msg_off[count];
   if (!c->vk_sk.ensure(32) || !c->vs_blob.ensure(end ? end : 16) || !c->vs_off.ensure((size_t)(count + 1) * 8) ||
@@ -2282,9 +2253,7 @@ int hbx_sign_msgs(hbx_ctx* c, const uint8_t* sk32, const uint8_t* msg_blob, cons
 // Decode p commitments of degree t and compute their rows at x (device state for the checks).
 static int bivar_rows_impl(hbx_ctx* c, const uint8_t* commit48, uint32_t p, uint32_t t, uint64_t x, bool want48) {
   if (!c || !commit48 || p == 0 || t > 4095) return fail(c, HBX_E_INVALID_ARG, "hbx_bivar: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, c->stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, c->stream);
   const size_t M = (size_t)(t + 1) * (t + 2) / 2, nr = (size_t)p * (t + 1);
   if (!c->bv_commit48.ensure(p * M * 48) || !c->bv_C.ensure(p * M * sizeof(g1a)) || !c->bv_cst.ensure(p * M * 4) ||
       !c->bv_rows.ensure(nr * sizeof(g1j)) || !c->bv_rows48.ensure(nr * 48) || !c->bv_pst.ensure(p))
@@ -2354,7 +2323,7 @@ static int combine_sigs_impl(hbx_ctx* c, const uint8_t* master_pk48, uint32_t t,
       !c->coin_ok.ensure(I) || !c->coin_par.ensure(I) || !c->coin_out96.ensure((size_t)I * 96) ||
       (d_use && !c->coin_use.ensure(m)))
     return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_combine_signatures: out of device memory");
-  if (c->coin_ready_ev) HIPCHK(c, hipStreamWaitEvent(s, c->coin_ready_ev, 0));
+  if (c->coin_ready_ev.e) HIPCHK(c, hipStreamWaitEvent(s, c->coin_ready_ev.e, 0));
   // the master key: decoded once per distinct value (era state; checked on the host)
   if (!c->coin_mpk_known || memcmp(c->coin_mpk48, master_pk48, 48) != 0) {
     HIPCHK(c, hipMemcpyAsync(c->coin_mpk_comp.p, master_pk48, 48, hipMemcpyHostToDevice, s));
@@ -2393,9 +2362,7 @@ static int combine_sigs_impl(hbx_ctx* c, const uint8_t* master_pk48, uint32_t t,
 int hbx_combine_signatures(hbx_ctx* c, const uint8_t* master_pk48, uint32_t t, uint8_t* sig96, int32_t* status,
                            uint8_t* master_ok_bits, uint8_t* parity_bits) {
   if (!c) return HBX_E_INVALID_ARG;
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, c->stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, c->stream);
   if (int rc = combine_sigs_impl(c, master_pk48, t, nullptr, s)) return rc;
   const uint32_t I = c->coin_I;
   std::vector<uint8_t> ok(I), par(I);
@@ -2414,9 +2381,7 @@ int hbx_combine_signatures(hbx_ctx* c, const uint8_t* master_pk48, uint32_t t, u
 int hbx_combine_signatures_d(hbx_ctx* c, const uint8_t* master_pk48, uint32_t t, const uint8_t* d_use, uint8_t* d_sig96,
                              int32_t* d_status, uint8_t* d_master_ok, uint8_t* d_parity, void* stream) {
   if (!c) return HBX_E_INVALID_ARG;
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, stream);
   if (int rc = combine_sigs_impl(c, master_pk48, t, d_use, s)) return rc;
   const uint32_t I = c->coin_I;
   if (d_sig96) HIPCHK(c, hipMemcpyAsync(d_sig96, c->coin_out96.p, (size_t)I * 96, hipMemcpyDeviceToDevice, s));
@@ -2429,9 +2394,7 @@ int hbx_combine_signatures_d(hbx_ctx* c, const uint8_t* master_pk48, uint32_t t,
 int hbx_get_ct_valid_d(hbx_ctx* c, uint8_t* d_ct_valid, void* stream) {
   if (!c || !d_ct_valid) return fail(c, HBX_E_INVALID_ARG, "hbx_get_ct_valid_d: bad args");
   if (c->p_ct == 0 || !c->ct_known) return fail(c, HBX_E_NO_CIPHERTEXTS, "ciphertext validity not computed yet");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, stream);
   HIPCHK(c, hipMemcpyAsync(d_ct_valid, c->ct_valid.p, c->p_ct, hipMemcpyDeviceToDevice, s));
   return HBX_OK;
 }
@@ -2455,17 +2418,15 @@ static int combine_impl(hbx_ctx* c, uint32_t t, uint8_t* d_out_blob, int32_t* d_
     }
     if (ncols == 0) return HBX_OK;
   }
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, stream);
   // the listed columns, consumed before the call returns (pinned staging, as the ragged descriptors)
   const uint32_t* d_cols = nullptr;
   const uint32_t pl = cols ? ncols : p;  // proposers of this launch
   if (cols) {
-    uint8_t* pin = rg_begin(c, (size_t)ncols * 4);
+    uint8_t* pin = staging_begin(c, (size_t)ncols * 4);
     if (!pin) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_combine_decrypt_cols_d: out of memory (staging)");
     memcpy(pin, cols, (size_t)ncols * 4);
-    if (int rc = rg_upload(c, (size_t)ncols * 4, s)) return rc;
+    if (int rc = staging_upload(c, (size_t)ncols * 4, s)) return rc;
     d_cols = c->rg_dev.as<uint32_t>();
   }
   if (!c->keys.ensure((size_t)p * 32) || !c->status.ensure((size_t)p * 4))
@@ -2548,31 +2509,64 @@ int hbx_decrypt_epoch_d(hbx_ctx* c, const uint8_t* d_u_comp, const uint8_t* d_v_
   return hbx_combine_decrypt_d(c, t, d_out_blob, d_status, stream);
 }
 
-int hbx_combine_decrypt(hbx_ctx* c, uint32_t t, uint8_t* out_blob, int32_t* status) {
-  if (!c || !out_blob) return fail(c, HBX_E_INVALID_ARG, "hbx_combine_decrypt: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
-  stream_scope ss_{c, pick(c, c->stream)};
-  if (c->p_ct == 0) return fail(c, HBX_E_NO_CIPHERTEXTS, "no ciphertexts prepared");
-  std::vector<uint64_t> off(c->p_ct + 1);
+// The host forms of the combine, on the context's stream: the offsets read back into `off`, out_own
+// sized, the _d call over `cols` (nullptr: every proposer, into a zeroed out_own and on to out_blob),
+// the statuses read back into `st`; synchronised at return.
+static int combine_host(hbx_ctx* c, uint32_t t, const uint32_t* cols, uint32_t ncols, uint8_t* out_blob,
+                        std::vector<uint64_t>& off, std::vector<int32_t>& st) {
+  const uint32_t p = c->p_ct;
+  if (p == 0) return fail(c, HBX_E_NO_CIPHERTEXTS, "no ciphertexts prepared");
+  off.resize(p + 1);
   HIPCHK(c, hipMemcpyAsync(off.data(), c->d_v_off, off.size() * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint64_t total = off[c->p_ct];
+  const uint64_t total = off[p];
   if (!c->out_own.ensure(total ? total : 16)) return fail(c, HBX_E_OUT_OF_MEMORY, "out of device memory");
-  HIPCHK(c, hipMemsetAsync(c->out_own.p, 0, total ? total : 16, c->stream));
-  int rc = hbx_combine_decrypt_d(c, t, c->out_own.as<uint8_t>(), nullptr, c->stream);
+  if (!cols) HIPCHK(c, hipMemsetAsync(c->out_own.p, 0, total ? total : 16, c->stream));
+  int rc = cols ? hbx_combine_decrypt_cols_d(c, t, cols, ncols, c->out_own.as<uint8_t>(), nullptr, c->stream)
+                : hbx_combine_decrypt_d(c, t, c->out_own.as<uint8_t>(), nullptr, c->stream);
   if (rc) return rc;
-  if (total) HIPCHK(c, hipMemcpyAsync(out_blob, c->out_own.p, total, hipMemcpyDeviceToHost, c->stream));
-  std::vector<int32_t> st(c->p_ct);
-  HIPCHK(c, hipMemcpyAsync(st.data(), c->status.p, (size_t)c->p_ct * 4, hipMemcpyDeviceToHost, c->stream));
+  if (!cols && total) HIPCHK(c, hipMemcpyAsync(out_blob, c->out_own.p, total, hipMemcpyDeviceToHost, c->stream));
+  st.resize(p);
+  HIPCHK(c, hipMemcpyAsync(st.data(), c->status.p, (size_t)p * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return HBX_OK;
+}
+
+int hbx_combine_decrypt(hbx_ctx* c, uint32_t t, uint8_t* out_blob, int32_t* status) {
+  if (!c || !out_blob) return fail(c, HBX_E_INVALID_ARG, "hbx_combine_decrypt: bad args");
+  HBX_ENTER(c, c->stream);
+  std::vector<uint64_t> off;
+  std::vector<int32_t> st;
+  if (int rc = combine_host(c, t, nullptr, 0, out_blob, off, st)) return rc;
   if (status) memcpy(status, st.data(), st.size() * 4);
   return HBX_OK;
 }
 
+int hbx_combine_decrypt_cols(hbx_ctx* c, uint32_t t, const uint32_t* cols, uint32_t ncols, uint8_t* out_blob,
+                             int32_t* status) {
+  if (!c || !out_blob || (!cols && ncols)) return fail(c, HBX_E_INVALID_ARG, "hbx_combine_decrypt_cols: bad args");
+  if (ncols == 0) return HBX_OK;
+  HBX_ENTER(c, c->stream);
+  std::vector<uint64_t> off;
+  std::vector<int32_t> st;
+  if (int rc = combine_host(c, t, cols, ncols, out_blob, off, st)) return rc;
+  // the listed proposers' entries and ranges only: nothing else of the caller's buffers is written
+  // (a proposer that did not decrypt has no plaintext: its range stays as the caller had it)
+  for (uint32_t k = 0; k < ncols; k++) {
+    const uint64_t a = off[cols[k]], b = off[cols[k] + 1];
+    if (status) status[cols[k]] = st[cols[k]];
+    if (st[cols[k]] == 0 && b > a)
+      HIPCHK(c, hipMemcpyAsync(out_blob + a, c->out_own.as<uint8_t>() + a, b - a, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return HBX_OK;
+}
+
 // ---- incremental share verification (include/hbx.h) ---------------------------------------------
+// addplan.hpp states the check kernels' tile shapes for the host: the two must agree
 static_assert(hbx_addplan::SHAPE_SENDERS[2] == (uint32_t)G3_PER_WAVE && hbx_addplan::SHAPE_SENDERS[3] == (uint32_t)G6_PER_WAVE &&
-                  hbx_addplan::FILL_WAVES == (size_t)VERIFY_FILL_WAVES && sizeof(hbx_addplan::tile) == sizeof(uint2),
-              "addplan.hpp restates the check kernels' tile shapes");
+                  sizeof(hbx_addplan::tile) == sizeof(uint2),
+              "addplan.hpp and the check kernels disagree on a tile's shape");
 
 int hbx_add_dec_shares_d(hbx_ctx* c, const uint8_t* d_shares48, const uint32_t* proposer, const uint32_t* sender,
                          uint32_t count, uint32_t n, uint8_t* d_status, void* stream) {
@@ -2596,7 +2590,7 @@ int hbx_add_dec_shares_d(hbx_ctx* c, const uint8_t* d_shares48, const uint32_t* 
     default:
       break;
   }
-  HIPCHK(c, hipSetDevice(c->device));
+  HBX_DEVICE(c);
   const size_t m = (size_t)n * p;
   if (!established) {
     // the matrix call with every share absent: own-share mode's entries and checks, a deferred
@@ -2625,12 +2619,12 @@ int hbx_add_dec_shares_d(hbx_ctx* c, const uint8_t* d_shares48, const uint32_t* 
   const std::vector<hbx_addplan::tile>& tiles = pl.tiles[hbx_addplan::shape_of_lanes(lanes)];
   // the items and the tile list, consumed before the call returns (pinned staging, one upload)
   const size_t items_bytes = (size_t)count * sizeof(uint2), tiles_bytes = tiles.size() * sizeof(uint2);
-  uint8_t* pin = rg_begin(c, items_bytes + tiles_bytes);
+  uint8_t* pin = staging_begin(c, items_bytes + tiles_bytes);
   if (!pin) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_add_dec_shares_d: out of memory (staging)");
   uint2* it = reinterpret_cast<uint2*>(pin);
   for (uint32_t k = 0; k < count; k++) it[k] = make_uint2(proposer[k], sender[k]);
   if (tiles_bytes) memcpy(pin + items_bytes, tiles.data(), tiles_bytes);
-  if (int rc = rg_upload(c, items_bytes + tiles_bytes, s)) return rc;
+  if (int rc = staging_upload(c, items_bytes + tiles_bytes, s)) return rc;
   const uint2* d_items = c->rg_dev.as<uint2>();
   const uint2* d_tiles = reinterpret_cast<const uint2*>(c->rg_dev.as<uint8_t>() + items_bytes);
   c->tab_ready = false;  // S is about to hold other shares than the tables were made from
@@ -2667,8 +2661,7 @@ int hbx_add_dec_shares(hbx_ctx* c, const uint8_t* shares48, const uint32_t* prop
                        uint32_t count, uint32_t n, uint8_t* status) {
   if (!c || n == 0 || (count && (!shares48 || !proposer || !sender)))
     return fail(c, HBX_E_INVALID_ARG, "hbx_add_dec_shares: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
-  stream_scope ss_{c, pick(c, c->stream)};
+  HBX_ENTER(c, c->stream);
   if (!c->add_shares.ensure((size_t)count * 48) || !c->add_dst.ensure(count))
     return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_add_dec_shares: out of device memory");
   if (count) HIPCHK(c, hipMemcpyAsync(c->add_shares.p, shares48, (size_t)count * 48, hipMemcpyHostToDevice, c->stream));
@@ -2684,41 +2677,12 @@ int hbx_add_dec_shares(hbx_ctx* c, const uint8_t* shares48, const uint32_t* prop
 
 uint32_t hbx_get_verify_tiles_used(const hbx_ctx* c) { return c ? c->verify_tiles : 0; }
 
-int hbx_combine_decrypt_cols(hbx_ctx* c, uint32_t t, const uint32_t* cols, uint32_t ncols, uint8_t* out_blob,
-                             int32_t* status) {
-  if (!c || !out_blob || (!cols && ncols)) return fail(c, HBX_E_INVALID_ARG, "hbx_combine_decrypt_cols: bad args");
-  if (ncols == 0) return HBX_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  stream_scope ss_{c, pick(c, c->stream)};
-  if (c->p_ct == 0) return fail(c, HBX_E_NO_CIPHERTEXTS, "no ciphertexts prepared");
-  std::vector<uint64_t> off(c->p_ct + 1);
-  HIPCHK(c, hipMemcpyAsync(off.data(), c->d_v_off, off.size() * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint64_t total = off[c->p_ct];
-  if (!c->out_own.ensure(total ? total : 16)) return fail(c, HBX_E_OUT_OF_MEMORY, "out of device memory");
-  int rc = hbx_combine_decrypt_cols_d(c, t, cols, ncols, c->out_own.as<uint8_t>(), nullptr, c->stream);
-  if (rc) return rc;
-  std::vector<int32_t> st(c->p_ct);
-  HIPCHK(c, hipMemcpyAsync(st.data(), c->status.p, (size_t)c->p_ct * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  // the listed proposers' entries and ranges only: nothing else of the caller's buffers is written
-  // (a proposer that did not decrypt has no plaintext: its range stays as the caller had it)
-  for (uint32_t k = 0; k < ncols; k++) {
-    const uint64_t a = off[cols[k]], b = off[cols[k] + 1];
-    if (status) status[cols[k]] = st[cols[k]];
-    if (st[cols[k]] == 0 && b > a)
-      HIPCHK(c, hipMemcpyAsync(out_blob + a, c->out_own.as<uint8_t>() + a, b - a, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return HBX_OK;
-}
-
 // ---- status readout ---------------------------------------------------------------------------
 static int copy_status(hbx_ctx* c, const dbuf& b, size_t have, uint8_t* out, size_t count, const char* what) {
   if (!out) return fail(c, HBX_E_INVALID_ARG, "%s: null output", what);
   if (have == 0) return fail(c, HBX_E_NO_CIPHERTEXTS, "%s: nothing computed yet", what);
   if (count != have) return fail(c, HBX_E_INVALID_ARG, "%s: count %zu, expected %zu", what, count, have);
-  HIPCHK(c, hipSetDevice(c->device));
+  HBX_DEVICE(c);
   HIPCHK(c, quiesce(c));  // the last results may have been enqueued on a caller's stream
   HIPCHK(c, hipMemcpy(out, b.p, have, hipMemcpyDeviceToHost));
   return HBX_OK;
@@ -2738,7 +2702,7 @@ int hbx_get_ct_hashes(hbx_ctx* c, uint8_t* h96, size_t count) {
   if (!c || !h96) return fail(c, HBX_E_INVALID_ARG, "hbx_get_ct_hashes: bad args");
   if (c->p_ct == 0) return fail(c, HBX_E_NO_CIPHERTEXTS, "hbx_get_ct_hashes: no ciphertexts prepared");
   if (count != c->p_ct) return fail(c, HBX_E_INVALID_ARG, "hbx_get_ct_hashes: count %zu, expected %u", count, c->p_ct);
-  HIPCHK(c, hipSetDevice(c->device));
+  HBX_DEVICE(c);
   HIPCHK(c, quiesce(c));
   dbuf out;
   if (!out.ensure(count * 96)) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_get_ct_hashes: out of device memory");
@@ -2748,7 +2712,6 @@ int hbx_get_ct_hashes(hbx_ctx* c, uint8_t* h96, size_t count) {
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e == hipSuccess) e = hipMemcpy(h96, out.p, count * 96, hipMemcpyDeviceToHost);
-  out.release();
   if (e != hipSuccess) return fail(c, HBX_E_DEVICE, "hbx_get_ct_hashes: %s", hipGetErrorString(e));
   return HBX_OK;
 }
@@ -2771,13 +2734,10 @@ static bool scalars_canonical(const uint8_t* s32, size_t count) {
 int hbx_public_keys(hbx_ctx* c, const uint8_t* sk32, uint32_t n, uint8_t* pk48) {
   if (!c || !sk32 || !pk48 || n == 0) return fail(c, HBX_E_INVALID_ARG, "hbx_public_keys: bad args");
   if (!scalars_canonical(sk32, n)) return fail(c, HBX_E_INVALID_ARG, "hbx_public_keys: scalar >= r");
-  HIPCHK(c, hipSetDevice(c->device));
-  stream_scope ss_{c, pick(c, c->stream)};
+  HBX_ENTER(c, c->stream);
   dbuf dsk, dpk;
-  if (!dsk.ensure((size_t)n * 32) || !dpk.ensure((size_t)n * 48)) {
-    dsk.release();
+  if (!dsk.ensure((size_t)n * 32) || !dpk.ensure((size_t)n * 48))
     return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_public_keys: out of device memory");
-  }
   int rc = HBX_OK;
   if (hipMemcpyAsync(dsk.p, sk32, (size_t)n * 32, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = HBX_E_DEVICE;
   if (rc == HBX_OK) {
@@ -2788,8 +2748,6 @@ int hbx_public_keys(hbx_ctx* c, const uint8_t* sk32, uint32_t n, uint8_t* pk48) 
         hipStreamSynchronize(c->stream) != hipSuccess)
       rc = HBX_E_DEVICE;
   }
-  dsk.release();
-  dpk.release();
   return rc ? fail(c, rc, "hbx_public_keys: device error") : HBX_OK;
 }
 
@@ -2802,17 +2760,12 @@ int hbx_encrypt(hbx_ctx* c, const uint8_t* pk48, const uint8_t* msg_blob, const 
     if (msg_off[j + 1] < msg_off[j]) return fail(c, HBX_E_INVALID_ARG, "hbx_encrypt: msg_off not monotone");
   const uint64_t total = msg_off[p];
   if (total && (!msg_blob || !v_blob)) return fail(c, HBX_E_INVALID_ARG, "hbx_encrypt: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
-  stream_scope ss_{c, pick(c, c->stream)};
+  HBX_ENTER(c, c->stream);
   dbuf dpkc, dpk, dst, dr, dm, doff, du, dv, dw;
-  dbuf* all[] = {&dpkc, &dpk, &dst, &dr, &dm, &doff, &du, &dv, &dw};
-  auto cleanup = [&]() { for (dbuf* b : all) b->release(); };
   if (!dpkc.ensure(48) || !dpk.ensure(sizeof(g1a)) || !dst.ensure(4) || !dr.ensure((size_t)p * 32) ||
       !dm.ensure(total) || !doff.ensure((size_t)(p + 1) * 8) || !du.ensure((size_t)p * 48) || !dv.ensure(total) ||
-      !dw.ensure((size_t)p * 96)) {
-    cleanup();
+      !dw.ensure((size_t)p * 96))
     return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_encrypt: out of device memory");
-  }
   int rc = HBX_OK;
   int32_t st = 0;
   bool ok = hipMemcpyAsync(dpkc.p, pk48, 48, hipMemcpyHostToDevice, c->stream) == hipSuccess &&
@@ -2826,10 +2779,8 @@ int hbx_encrypt(hbx_ctx* c, const uint8_t* pk48, const uint8_t* msg_blob, const 
          hipMemcpyAsync(&st, dst.p, 4, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
          hipStreamSynchronize(c->stream) == hipSuccess;
   }
-  if (ok && st != HBX_PT_OK) {
-    cleanup();
+  if (ok && st != HBX_PT_OK)
     return fail(c, HBX_E_INVALID_ARG, "hbx_encrypt: public key does not decode (status %d)", st);
-  }
   if (ok) {
     hipLaunchKernelGGL(k_encrypt, dim3((p + 63) / 64), dim3(64), 0, c->stream, dpk.as<g1a>(), dr.as<uint8_t>(),
                        dm.as<uint8_t>(), doff.as<uint64_t>(), p, du.as<uint8_t>(), dv.as<uint8_t>(), dw.as<uint8_t>(),
@@ -2841,7 +2792,6 @@ int hbx_encrypt(hbx_ctx* c, const uint8_t* pk48, const uint8_t* msg_blob, const 
          hipStreamSynchronize(c->stream) == hipSuccess;
   }
   if (!ok) rc = HBX_E_DEVICE;
-  cleanup();
   return rc ? fail(c, rc, "hbx_encrypt: device error") : HBX_OK;
 }
 
@@ -2850,17 +2800,12 @@ int hbx_decrypt_shares(hbx_ctx* c, const uint8_t* sk32, uint32_t n, const uint8_
   if (!c || !sk32 || !u48 || !shares48 || n == 0 || p == 0)
     return fail(c, HBX_E_INVALID_ARG, "hbx_decrypt_shares: bad args");
   if (!scalars_canonical(sk32, n)) return fail(c, HBX_E_INVALID_ARG, "hbx_decrypt_shares: scalar >= r");
-  HIPCHK(c, hipSetDevice(c->device));
-  stream_scope ss_{c, pick(c, c->stream)};
+  HBX_ENTER(c, c->stream);
   const size_t m = (size_t)n * p;
   dbuf dsk, duc, du, dst, dout;
-  dbuf* all[] = {&dsk, &duc, &du, &dst, &dout};
-  auto cleanup = [&]() { for (dbuf* b : all) b->release(); };
   if (!dsk.ensure((size_t)n * 32) || !duc.ensure((size_t)p * 48) || !du.ensure((size_t)p * sizeof(g1a)) ||
-      !dst.ensure((size_t)p * 4) || !dout.ensure(m * 48)) {
-    cleanup();
+      !dst.ensure((size_t)p * 4) || !dout.ensure(m * 48))
     return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_decrypt_shares: out of device memory");
-  }
   std::vector<int32_t> st(p);
   bool ok = hipMemcpyAsync(dsk.p, sk32, (size_t)n * 32, hipMemcpyHostToDevice, c->stream) == hipSuccess &&
             hipMemcpyAsync(duc.p, u48, (size_t)p * 48, hipMemcpyHostToDevice, c->stream) == hipSuccess;
@@ -2872,10 +2817,8 @@ int hbx_decrypt_shares(hbx_ctx* c, const uint8_t* sk32, uint32_t n, const uint8_
          hipStreamSynchronize(c->stream) == hipSuccess;
   }
   for (uint32_t j = 0; ok && j < p; j++)
-    if (st[j] != HBX_PT_OK && st[j] != HBX_PT_INFINITY) {
-      cleanup();
+    if (st[j] != HBX_PT_OK && st[j] != HBX_PT_INFINITY)
       return fail(c, HBX_E_INVALID_ARG, "hbx_decrypt_shares: U_%u does not decode (status %d)", j, st[j]);
-    }
   if (ok) {
     hipLaunchKernelGGL(k_decrypt_shares, dim3((n + 63) / 64, p), dim3(64), 0, c->stream, dsk.as<uint8_t>(), n,
                        du.as<g1a>(), dout.as<uint8_t>());
@@ -2883,16 +2826,11 @@ int hbx_decrypt_shares(hbx_ctx* c, const uint8_t* sk32, uint32_t n, const uint8_
          hipMemcpyAsync(shares48, dout.p, m * 48, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
          hipStreamSynchronize(c->stream) == hipSuccess;
   }
-  cleanup();
   return ok ? HBX_OK : fail(c, HBX_E_DEVICE, "hbx_decrypt_shares: device error");
 }
 
 // ---- SyncKeyGen (src/sync_key_gen.rs) beyond the commitment checks -----------------------------
 namespace {
-// device buffer of one call
-struct kg_tmp : dbuf {
-  ~kg_tmp() { release(); }
-};
 // Ciphertexts per Ciphertext::verify pass of hbx_sk_decrypt.  The prepared-ciphertext state is about
 // 100 KiB per ciphertext (two sets of 2 x 68 Miller lines and their scratch), so 1024 bound it near
 // 100 MiB however many ciphertexts a call brings (N^2 = 65,536 at N = 256).  A larger chunk would not
@@ -2920,10 +2858,8 @@ int hbx_encrypt_to(hbx_ctx* c, const uint8_t* pk48, const uint8_t* msg_blob, con
     if (msg_off[j + 1] < msg_off[j]) return fail(c, HBX_E_INVALID_ARG, "hbx_encrypt_to: msg_off not monotone");
   const uint64_t total = msg_off[count];
   if (total && (!msg_blob || !v_blob)) return fail(c, HBX_E_INVALID_ARG, "hbx_encrypt_to: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, c->stream);
-  stream_scope ss_{c, s};
-  kg_tmp dpkc, dpk, dst, dr, dm, doff, du, dv, dw;
+  HBX_ENTER(c, c->stream);
+  dbuf dpkc, dpk, dst, dr, dm, doff, du, dv, dw;
   if (!dpkc.ensure((size_t)count * 48) || !dpk.ensure((size_t)count * sizeof(g1a)) || !dst.ensure((size_t)count * 4) ||
       !dr.ensure((size_t)count * 32) || !dm.ensure(total) || !doff.ensure((size_t)(count + 1) * 8) ||
       !du.ensure((size_t)count * 48) || !dv.ensure(total) || !dw.ensure((size_t)count * 96))
@@ -2965,9 +2901,7 @@ int hbx_sk_decrypt(hbx_ctx* c, const uint8_t* sk32, const uint8_t* u48, const ui
   }
   const uint64_t total = v_off[count];
   if (total && (!v_blob || !out_blob)) return fail(c, HBX_E_INVALID_ARG, "hbx_sk_decrypt: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, c->stream);
-  stream_scope ss_{c, s};
+  HBX_ENTER(c, c->stream);
   if (!c->u_comp_own.ensure((size_t)count * 48) || !c->w_comp_own.ensure((size_t)count * 96) ||
       !c->v_off_own.ensure((size_t)(count + 1) * 8) || !c->v_blob_own.ensure(total ? total : 16) ||
       !c->kg_out.ensure(total ? total : 16) || !c->kg_st.ensure(count) || !c->kg_sk.ensure(32))
@@ -3046,10 +2980,7 @@ int hbx_sk_decrypt(hbx_ctx* c, const uint8_t* sk32, const uint8_t* u48, const ui
   c->own_me = saved_me;
   c->own_ready = false;
   c->p_ct = 0;
-  c->ct_known = false;
-  c->n_shares = 0;
-  c->verified_p = 0;
-  c->tab_ready = false;
+  c->invalidate_epoch();
   if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(status, c->kg_st.p, count, hipMemcpyDeviceToHost, s));
   if (total) HIPCHK(c, hipMemcpyAsync(out_blob, c->kg_out.p, total, hipMemcpyDeviceToHost, s));
@@ -3062,10 +2993,8 @@ int hbx_bivar_poly_rows(hbx_ctx* c, const uint8_t* coeff32, uint32_t t, uint32_t
   const size_t M = (size_t)(t + 1) * (t + 2) / 2, lanes = (size_t)n * (t + 1);
   if (lanes > (size_t)1 << 30) return fail(c, HBX_E_INVALID_ARG, "hbx_bivar_poly_rows: n (t + 1) too large");
   if (!scalars_canonical(coeff32, M)) return fail(c, HBX_E_INVALID_ARG, "hbx_bivar_poly_rows: scalar >= r");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, c->stream);
-  stream_scope ss_{c, s};
-  kg_tmp dc, dout;
+  HBX_ENTER(c, c->stream);
+  dbuf dc, dout;
   if (!dc.ensure(M * 32) || !dout.ensure(lanes * 32))
     return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_bivar_poly_rows: out of device memory");
   HIPCHK(c, hipMemcpyAsync(dc.p, coeff32, M * 32, hipMemcpyHostToDevice, s));
@@ -3083,10 +3012,8 @@ int hbx_fr_poly_eval(hbx_ctx* c, const uint8_t* coeff32, uint32_t p, uint32_t t,
   const size_t nc = (size_t)p * (t + 1), lanes = (size_t)p * n;
   if (lanes > (size_t)1 << 30 || nc > (size_t)1 << 30) return fail(c, HBX_E_INVALID_ARG, "hbx_fr_poly_eval: too large");
   if (!scalars_canonical(coeff32, nc)) return fail(c, HBX_E_INVALID_ARG, "hbx_fr_poly_eval: scalar >= r");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, c->stream);
-  stream_scope ss_{c, s};
-  kg_tmp dc, dout;
+  HBX_ENTER(c, c->stream);
+  dbuf dc, dout;
   if (!dc.ensure(nc * 32) || !dout.ensure(lanes * 32))
     return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_fr_poly_eval: out of device memory");
   HIPCHK(c, hipMemcpyAsync(dc.p, coeff32, nc * 32, hipMemcpyHostToDevice, s));
@@ -3117,10 +3044,8 @@ int hbx_keygen_generate(hbx_ctx* c, const uint8_t* commit48, uint32_t p, uint32_
           if (y[a] == y[b]) return fail(c, HBX_E_DUPLICATE_ENTRY, "hbx_keygen_generate: part %u repeats y = %llu", q, (unsigned long long)y[a]);
     }
   }
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, c->stream);
-  stream_scope ss_{c, s};
-  kg_tmp dcomp, dcnt, dy, dv, dpkc, dpart, dsk;
+  HBX_ENTER(c, c->stream);
+  dbuf dcomp, dcnt, dy, dv, dpkc, dpart, dsk;
   if (!c->bv_commit48.ensure(p * M * 48) || !c->bv_C.ensure(p * M * sizeof(g1a)) || !c->bv_cst.ensure(p * M * 4) ||
       !dcomp.ensure(p) || !dpkc.ensure((size_t)(t + 1) * 48) ||
       (sk32_out && (!dcnt.ensure((size_t)p * 4) || !dy.ensure(nv * 8) || !dv.ensure(nv * 32) ||
@@ -3168,10 +3093,8 @@ int hbx_keygen_generate(hbx_ctx* c, const uint8_t* commit48, uint32_t p, uint32_
 int hbx_pk_shares_from_commit(hbx_ctx* c, const uint8_t* pk_commit48, uint32_t t, uint32_t n, uint8_t* pk48) {
   if (!c || !pk_commit48 || !pk48 || n == 0 || t > 4095)
     return fail(c, HBX_E_INVALID_ARG, "hbx_pk_shares_from_commit: bad args");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = pick(c, c->stream);
-  stream_scope ss_{c, s};
-  kg_tmp dcc, dP, dst, dout;
+  HBX_ENTER(c, c->stream);
+  dbuf dcc, dP, dst, dout;
   if (!dcc.ensure((size_t)(t + 1) * 48) || !dP.ensure((size_t)(t + 1) * sizeof(g1a)) || !dst.ensure((size_t)(t + 1) * 4) ||
       !dout.ensure((size_t)n * 48))
     return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_pk_shares_from_commit: out of device memory");
@@ -3196,24 +3119,26 @@ int hbx_pk_shares_from_commit(hbx_ctx* c, const uint8_t* pk_commit48, uint32_t t
 
 int hbx_set_timing(hbx_ctx* c, int on) {
   if (!c) return HBX_E_INVALID_ARG;
-  HIPCHK(c, hipSetDevice(c->device));
-  timing_reset(c);
-  c->timing = on != 0;
+  HBX_DEVICE(c);
+  c->timing.reset();
+  c->timing.on = on != 0;
   return HBX_OK;
 }
 
 int hbx_kernel_time(hbx_ctx* c, int kernel, double* total_ms, uint32_t* launches) {
   if (!c || kernel < 0 || kernel >= HBX_K_COUNT || !total_ms) return fail(c, HBX_E_INVALID_ARG, "hbx_kernel_time: bad argument");
-  HIPCHK(c, hipSetDevice(c->device));
+  HBX_DEVICE(c);
   double tot = 0;
-  for (auto& pr : c->tev[kernel]) {
+  for (auto& pr : c->timing.tev[kernel]) {
     HIPCHK(c, hipEventSynchronize(pr.second));
     float ms = 0;
     HIPCHK(c, hipEventElapsedTime(&ms, pr.first, pr.second));
     tot += ms;
   }
   *total_ms = tot;
-  if (launches) *launches = (uint32_t)c->tev[kernel].size();
+  if (launches) *launches = (uint32_t)c->timing.tev[kernel].size();
   return HBX_OK;
 }
+
+uint64_t hbx_debug_live_buffers(void) { return live_buffers.load(); }
 #endif  // host translation unit

@@ -115,6 +115,7 @@ EXPORTS = (
     "hbx_combine_decrypt_cols_d",
     "hbx_combine_decrypt_cols",
     "hbx_get_verify_tiles_used",
+    "hbx_debug_live_buffers",
 )
 
 DIGEST_SHA256 = 0
@@ -291,8 +292,17 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.hbx_combine_decrypt_cols.argtypes = [P, u32, u32p, u32, u8p, i32p]
         lib.hbx_get_verify_tiles_used.argtypes = [P]
         lib.hbx_get_verify_tiles_used.restype = u32
+    # the live-allocation count: absent from a library built before it
+    if hasattr(lib, "hbx_debug_live_buffers"):
+        lib.hbx_debug_live_buffers.argtypes = []
+        lib.hbx_debug_live_buffers.restype = ctypes.c_uint64
     _lib = lib
     return lib
+
+
+def live_buffers() -> int:
+    """hbx_debug_live_buffers: device and pinned allocations the library holds in this process."""
+    return int(load_library().hbx_debug_live_buffers())
 
 
 def build_info() -> dict:

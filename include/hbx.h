@@ -202,6 +202,9 @@ int hbx_set_combine_lanes(hbx_ctx* ctx, int lanes);
 #define HBX_COMBINE_TABLES_OFF (-2)
 int hbx_debug_set_combine_margin(hbx_ctx* ctx, int32_t margin);
 int64_t hbx_get_combine_slow_terms(hbx_ctx* ctx);
+/* Device and pinned allocations the library currently holds in this process, over all contexts
+ * (tests: a destroyed context, and a call that failed, leave none behind). */
+uint64_t hbx_debug_live_buffers(void);
 /* Batched decryption-share verification by random linear combination (no reference counterpart;
  * statuses identical except with probability <= 2^-128 per column, DESIGN.md "Batched share
  * verification").  seed32 != NULL: hbx_verify_dec_shares[_d] and hbx_decrypt_epoch_d decide each

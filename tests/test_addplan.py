@@ -138,6 +138,25 @@ def test_lane_ladder_boundaries(ap):
         assert ap.ap_choose_lanes(*t) == model_ladder(*t)
 
 
+# (n, p, lanes) of a full p x n matrix.  Each value is worked out by hand from the ladder the matrix
+# verification has always stated (one lane when ceil(n/64) p >= 1024; else six when ceil(n/10) p <=
+# 1024; else three when ceil(n/21) p <= 1024; else two when ceil(n/32) p <= 1024; else three):
+#   256 x 256: t1 = 4 * 256 = 1024 -> 1        10 x 10: t6 = 10 -> 6        64 x 64: t6 = 7 * 64 = 448 -> 6
+#   128 x 32: t6 = 13 * 32 = 416 -> 6          256 x 32: t6 = 26 * 32 = 832 -> 6
+#   256 x 64: t6 = 1664, t3 = 13 * 64 = 832 -> 3
+#   256 x 96: t6 = 2496, t3 = 1248, t2 = 8 * 96 = 768 -> 2
+#   256 x 128: t6 = 3328, t3 = 1664, t2 = 8 * 128 = 1024, t1 = 512 -> 2
+FULL_MATRIX_LANES = [(256, 256, 1), (10, 10, 6), (64, 64, 6), (128, 32, 6), (256, 32, 6), (256, 64, 3), (256, 96, 2),
+                     (256, 128, 2)]
+
+
+def test_full_matrix_lanes(ap):
+    """The matrix verification takes its lanes from choose_lanes over the whole matrix's tile counts."""
+    for n, p, lanes in FULL_MATRIX_LANES:
+        t1, t2, t3, t6 = (-(-n // per) * p for per in SENDERS)
+        assert ap.ap_choose_lanes(t1, t6, t3, t2) == lanes, (n, p)
+
+
 def test_rejections(ap):
     assert plan(ap, [(0, 1), (1, 1), (0, 1)], 7, 3, 0)[0] == -2  # the same pair twice
     assert plan(ap, [(0, 9), (0, 9)], 7, 3, 0)[0] == -2  # ... also of an unknown sender
