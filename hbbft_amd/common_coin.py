@@ -22,6 +22,11 @@ FaultLog, errors, messages and outputs, in the same order, with ONE engine pass 
    the reference keeps the instance open and retries on a later share) is remembered and the
    replay runs again, so the retries happen exactly where the reference would run them.
 
+``CoinReplay`` decides a finished round.  ``CoinSession`` (below) serves a node that is running
+one: the messages are fed as they arrive, each flush appends its shares to the matrix the context
+holds (``hbx_add_sig_shares_d``) and combines only the instances that triggered
+(``hbx_combine_signatures_insts_d``), with the same results whatever the flush schedule.
+
 Message model: see ``oracle/common_coin.py`` (the message-at-a-time restatement this is tested
 against): ``("input", inst)`` and ``("share", sender, inst, sig96)``.
 """
@@ -32,7 +37,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .hbx import SHARE_INVALID, SHARE_UNDECODABLE, SHARE_VALID
+from .hbx import SHARE_INVALID, SHARE_UNDECODABLE, SHARE_UNKNOWN_SENDER, SHARE_VALID
 
 UNVERIFIED_SIGNATURE_SHARE_SENDER = "UnverifiedSignatureShareSender"
 UNKNOWN_SENDER = "UnknownSender"
@@ -300,3 +305,228 @@ class CoinReplay:
         for inst, held in pending.items():
             err = COMBINE_FAILED if st[inst] != 0 else None if ok[inst] else VERIFICATION_FAILED
             known[(inst, held)] = (err, bool(par[inst]))
+
+
+# ---- a node that is running its coin instances (hbx_add_sig_shares_d) -----------------------------
+class GpuCoinAddEngine(GpuCoinEngine):
+    """``GpuCoinEngine`` plus the incremental calls: ``add`` appends signature shares to the round's
+    matrix in the context (``hbx_add_sig_shares_d``), ``combine_insts`` combines the listed
+    instances (``hbx_combine_signatures_insts_d``)."""
+
+    def add(self, sig96: np.ndarray, inst, sender, n: int) -> np.ndarray:
+        """sig96 uint8[k, 96] for positions (inst[k], sender[k]) -> HBX_SHARE_* uint8[k]."""
+        torch = self.torch
+        dev = torch.device("cuda", self.ctx.device)
+        k = len(inst)
+        if k == 0:
+            self.ctx.add_sig_shares_d(None, [], [], n, stream=self.stream)
+            return np.zeros(0, dtype=np.uint8)
+        d_sig = torch.from_numpy(np.array(sig96, dtype=np.uint8, order="C")).to(dev)  # a writable copy for torch
+        d_st = torch.zeros(k, dtype=torch.uint8, device=dev)
+        self.ctx.add_sig_shares_d(d_sig, inst, sender, n, d_st, stream=self.stream)
+        return d_st.cpu().numpy()
+
+    def combine_insts(self, insts, use: np.ndarray, t: int):
+        """The listed instances over the matrix's VALID entries restricted to ``use`` -> (status
+        int32[count], master_ok bool[count], parity bool[count]); only the listed entries mean
+        anything."""
+        torch = self.torch
+        count = use.shape[0]
+        dev = torch.device("cuda", self.ctx.device)
+        d_use = torch.from_numpy(np.ascontiguousarray(use, dtype=np.uint8)).to(dev)
+        d_st = torch.zeros(count, dtype=torch.int32, device=dev)
+        d_ok = torch.zeros(count, dtype=torch.uint8, device=dev)
+        d_par = torch.zeros(count, dtype=torch.uint8, device=dev)
+        self.ctx.combine_signatures_insts_d(self.master_pk48, t, insts, d_use, None, d_st, d_ok, d_par, stream=self.stream)
+        return d_st.cpu().numpy(), d_ok.cpu().numpy().astype(bool), d_par.cpu().numpy().astype(bool)
+
+
+class CoinSession:
+    """Every CommonCoin instance of a round at node ``me`` (None: an observer), fed as the messages
+    arrive: ``prepare(nonces)`` once, ``handle(event)`` queues an event, ``flush()`` runs the queued
+    events and returns what they added -- faults, errors, sent, outputs and combines, as a
+    ``CoinResult``.  Whatever the flush schedule, the results in flush order are what the reference
+    emits message by message (``oracle/common_coin.py`` ``CoinNode.run``).
+
+    Per flush: our own share of the instances that get their first input goes through the same
+    checks as a received one (common_coin.rs:142-146); the queued shares -- except those of an
+    instance that terminated before the flush, which never reach the engine (:105-110) -- are
+    appended to the round's matrix with one ``add`` per layer of repeated (instance, sender) pairs
+    (``hbx_add_sig_shares_d``: only the touched tiles are checked, the shares held from earlier
+    flushes stay on the device); the reference's control flow is replayed over the status bytes;
+    the instances whose ``try_output`` would combine are combined in one ``combine_insts``
+    (``hbx_combine_signatures_insts_d``) with ``use`` = the shares held at the trigger; a combination
+    that fails the master check (``VerificationFailed``) leaves its instance open and the replay
+    runs again, so the retry happens where the reference retries.
+
+    ``ctx``: an ``hbx.Context`` holding the era's key shares, or with ``engine=`` any object with
+    ``prepare`` / ``sign`` / ``add`` / ``combine_insts`` (tests)."""
+
+    def __init__(self, ctx, master_pk48: bytes, n: int, me: Optional[int], sk32: Optional[bytes] = None, engine=None,
+                 stream=None):
+        self.engine = engine if engine is not None else GpuCoinAddEngine(ctx, master_pk48, sk32, stream)
+        self.n = n
+        self.f = (n - 1) // 3  # NetworkInfo::num_faulty, messaging.rs:258
+        self.t = self.f + 1    # combine_signatures needs threshold + 1 shares
+        self.me = me
+        self.count = 0
+        self.engine_adds = 0      # engine add calls so far (one per layer per flush)
+        self.engine_combines = 0  # engine combine calls so far
+        self._queue: List[tuple] = []
+        self._insts: List[_Inst] = []
+        self._own: Optional[np.ndarray] = None
+        self._known: Dict[Tuple[int, Tuple[int, ...]], Tuple[Optional[str], bool]] = {}
+
+    def prepare(self, nonces):
+        nonces = list(nonces)
+        self.engine.prepare(nonces)
+        self.count = len(nonces)
+        self._insts = [_Inst() for _ in range(self.count)]
+        self._queue, self._own, self._known = [], None, {}
+        self.engine.add(np.zeros((0, 96), dtype=np.uint8), [], [], self.n)  # the round's matrix: every share absent
+        self.engine_adds = self.engine_combines = 0
+
+    def handle(self, event):
+        if event[0] not in ("input", "share"):
+            raise ValueError(event[0])
+        self._queue.append(event)
+
+    # ------------------------------------------------------------------------------------------
+    def flush(self) -> CoinResult:
+        events, self._queue = self._queue, []
+        n = self.n
+        # the share messages of this flush: received ones and, at our first input to an instance, our own
+        msgs: List[Tuple[int, int, bytes]] = []  # (inst, sender as the engine sees it, sig96)
+        msg_of_event: Dict[int, int] = {}
+        seen_input = {q for q, b in enumerate(self._insts) if b.had_input}
+        for k, ev in enumerate(events):
+            if ev[0] == "input":
+                inst = ev[1]
+                if self.me is not None and inst not in seen_input:
+                    if self._own is None:
+                        self._own = self.engine.sign()
+                    msg_of_event[k] = len(msgs)
+                    msgs.append((inst, self.me, bytes(self._own[inst])))
+                seen_input.add(inst)
+            else:
+                _, sender, inst, sig96 = ev
+                if self._insts[inst].terminated:
+                    continue  # handle_message after termination (:105-110): never verified
+                msg_of_event[k] = len(msgs)
+                # a sender outside 0..n-1 touches no position; the engine still says whether serde decodes it
+                msgs.append((inst, sender if 0 <= sender < 0xFFFFFFFF else 0xFFFFFFFF, bytes(sig96)))
+        status = self._add(msgs)
+        res_status: List[Optional[int]] = [None] * len(events)
+        for k, m in msg_of_event.items():
+            if events[k][0] == "share" and 0 <= events[k][1] < n:
+                res_status[k] = int(status[m])
+        combines_run = 0
+        while True:
+            res, pending, insts = self._replay(events, msgs, msg_of_event, status)
+            if not pending:
+                break
+            combines_run += 1
+            self._combine(pending)
+        self._insts = insts
+        self.engine_combines += combines_run
+        res.share_status = res_status
+        res.engine_combines = combines_run
+        return res
+
+    def _add(self, msgs) -> np.ndarray:
+        """One engine add per layer (layer L = the L-th message of each (inst, sender) pair in this
+        flush), in order, so the matrix ends as message-by-message delivery leaves it."""
+        status = np.full(len(msgs), SHARE_UNDECODABLE, dtype=np.int32)
+        layers: List[List[int]] = []
+        seen: Dict[Tuple[int, int], int] = {}
+        for m, (inst, sender, _) in enumerate(msgs):
+            L = seen.get((inst, sender), 0)
+            seen[(inst, sender)] = L + 1
+            if L == len(layers):
+                layers.append([])
+            layers[L].append(m)
+        for layer in layers:
+            sig = np.frombuffer(b"".join(msgs[m][2] for m in layer), dtype=np.uint8).reshape(len(layer), 96)
+            st = self.engine.add(sig, [msgs[m][0] for m in layer], [msgs[m][1] for m in layer], self.n)
+            self.engine_adds += 1
+            status[layer] = st
+        return status
+
+    def _replay(self, events, msgs, msg_of_event, status):
+        res = CoinResult()
+        insts = []
+        for b in self._insts:
+            c = _Inst()
+            c.had_input, c.terminated, c.received = b.had_input, b.terminated, dict(b.received)
+            insts.append(c)
+        pending: Dict[int, Tuple[int, ...]] = {}  # inst -> the senders held at the trigger
+
+        def try_output(inst, who):
+            b = insts[inst]
+            if not (b.had_input and len(b.received) > self.f):
+                return
+            senders = tuple(sorted(b.received))
+            r = self._known.get((inst, senders))
+            if r is None:
+                pending[inst] = senders  # combined after this pass; taken to succeed meanwhile
+                b.terminated = True
+                return
+            err, par = r
+            res.combines.append((inst, senders, err is None))
+            if err is not None:
+                res.errors.append((who, err))
+                return
+            b.terminated = True
+            res.outputs.append((inst, par))
+
+        def handle_share(inst, sender, m, who):
+            st = status[m]
+            if st == SHARE_UNKNOWN_SENDER:
+                res.errors.append((who, UNKNOWN_SENDER))
+                return
+            if st != SHARE_VALID:
+                if st == SHARE_INVALID:
+                    res.faults.append((sender, UNVERIFIED_SIGNATURE_SHARE_SENDER))
+                return
+            insts[inst].received[sender] = m
+            try_output(inst, who)
+
+        for k, ev in enumerate(events):
+            if ev[0] == "input":
+                inst = ev[1]
+                b = insts[inst]
+                if b.had_input:
+                    continue
+                b.had_input = True
+                if self.me is None:
+                    try_output(inst, None)
+                    continue
+                m = msg_of_event[k]
+                # get_coin (common_coin.rs:142-146): an error from our own share's handle_share
+                # drops the step with the outgoing message (the `?`); the error is our input's
+                n_err = len(res.errors)
+                handle_share(inst, self.me, m, None)
+                if len(res.errors) == n_err:
+                    res.sent.append((inst, msgs[m][2]))
+            else:
+                _, sender, inst, _ = ev
+                m = msg_of_event.get(k)
+                if m is None or status[m] == SHARE_UNDECODABLE:
+                    continue  # terminated before the flush, or rejected by serde before CommonCoin
+                if insts[inst].terminated:
+                    continue  # handle_message after termination (:105-110)
+                if not 0 <= sender < self.n:
+                    res.errors.append((sender, UNKNOWN_SENDER))
+                    continue
+                handle_share(inst, sender, m, sender)
+        return res, pending, insts
+
+    def _combine(self, pending):
+        """One engine combine over the instances that triggered, each over the shares it held then."""
+        use = np.zeros((self.count, self.n), dtype=np.uint8)
+        for inst, senders in pending.items():
+            use[inst, list(senders)] = 1
+        st, ok, par = self.engine.combine_insts(sorted(pending), use, self.t)
+        for inst, senders in pending.items():
+            err = COMBINE_FAILED if st[inst] != 0 else None if ok[inst] else VERIFICATION_FAILED
+            self._known[(inst, senders)] = (err, bool(par[inst]))

@@ -237,6 +237,17 @@ struct hbx_ctx {
   uint8_t coin_mpk48[48] = {0};   // the master key coin_mpk was decoded from
   bool coin_mpk_known = false;
   dbuf coin_use;      // hbx_combine_signatures_d: the verified shares masked by the caller's subset
+  // hbx_add_sig_shares_d: coin_live = the [coin_I][coin_n] matrix belongs to the prepared nonces and
+  // the current keys (read by the add alone: a matrix verification or an add sets it;
+  // hbx_prepare_nonces, hbx_set_digest and hbx_set_pk_shares clear it).  The candidates of an add are
+  // decoded and checked apart from the round's matrix (same layout; only the add's tiles are ever
+  // written or read), coin_add_mask holds the add's positions as the tile launch's present mask (all
+  // 0 between calls; coin_add_mask_m = the bytes known to be 0), coin_add_ist the statuses of the
+  // items that touch no position; then the host forms' staging.
+  bool coin_live = false;
+  uint32_t coin_tiles = 0;  // check blocks of the last signature-share launch (hbx_get_coin_tiles_used)
+  dbuf coin_add_sig, coin_add_st, coin_add_valid, coin_add_mask, coin_add_ist, coin_add_sig96, coin_add_dst, coin_use_in;
+  size_t coin_add_mask_m = 0;
   // SyncKeyGen commitment checks (hbx_bivar_rows / hbx_bivar_check_acks)
   dbuf bv_commit48, bv_C, bv_cst, bv_rows, bv_rows48, bv_pst, bv_ackp, bv_acky, bv_vals, bv_out;
   // SyncKeyGen SecretKey::decrypt (hbx_sk_decrypt): the key's limbs, plaintexts, HBX_CT_* per ciphertext
@@ -682,6 +693,7 @@ int hbx_set_digest(hbx_ctx* c, int variant) {
   c->invalidate_epoch();
   c->coin_I = 0;
   c->coin_n = 0;
+  c->coin_live = false;
   return HBX_OK;
 }
 
@@ -835,6 +847,7 @@ int hbx_set_pk_shares(hbx_ctx* c, const uint8_t* pk_comp, uint32_t n, int32_t* s
   c->p_ct = 0;
   c->invalidate_epoch();
   c->coin_n = 0;
+  c->coin_live = false;
   if (!c->pk.ensure((size_t)n * sizeof(g1a)) || !c->pk_m.ensure((size_t)n * sizeof(g1a)) ||
       !c->pk64.ensure((size_t)n * sizeof(g1a)) || !c->pk_status.ensure((size_t)n * 4) || !c->pk_comp.ensure((size_t)n * 48))
     return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_set_pk_shares: out of device memory");
@@ -1921,6 +1934,7 @@ int hbx_prepare_nonces(hbx_ctx* c, const uint8_t* nonce_blob, const uint64_t* no
   // hbx_sign and h96 (coin_true_h): the share checks and the combine work on H' = [m] H
   c->coin_lines_ready = false;
   c->coin_h_ready = false;
+  c->coin_live = false;  // the matrix of an earlier round is not of these nonces (hbx_add_sig_shares_d)
   c->coin_I = count;
   if (h96) {
     if (int rc = coin_true_h(c, s)) return rc;
@@ -1954,6 +1968,68 @@ int hbx_sign(hbx_ctx* c, const uint8_t* sk32, uint32_t n, uint8_t* sig96) {
   return HBX_OK;
 }
 
+// H''s prepared lines (wave-uniform loads) of the prepared nonces, once per hbx_prepare_nonces: the
+// one-lane kernel's mixed loop, and since round 6 the two-lane kernel's H' pair (its lanes then
+// generate only sigma's lines, together).
+static int coin_prepare_lines(hbx_ctx* c, hipStream_t s) {
+  if (c->coin_lines_ready) return HBX_OK;
+  const uint32_t count = c->coin_I;
+  timed t_(c, HBX_K_PREPARE_LINES, s);
+  hipLaunchKernelGGL(k_prepare_lines<true>, dim3((count * LINE_K + 63) / 64), dim3(64), 0, s, c->coin_Hp.as<g2a>(), count,
+                     c->coin_lines_d.as<line_pre_d>(), c->coin_scratch.as<fq2d>(), nullptr, 0u, nullptr, nullptr, nullptr, 1u,
+                     UINT32_MAX, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0u);
+  HIPCHK(c, hipGetLastError());
+  const uint32_t nl = count * MILLER_LINES;
+  hipLaunchKernelGGL(k_normalise_lines, dim3((nl + 63) / 64), dim3(64), 0, s, c->coin_lines.as<line_pre>(),
+                     c->coin_scratch.as<fq2d>(), nl, c->coin_lines_d.as<line_pre_d>(), nullptr, nullptr, nullptr, nullptr);
+  HIPCHK(c, hipGetLastError());
+  c->coin_lines_ready = true;
+  // the lines are built on this call's stream: move the prepare event past them, so a later
+  // one-lane check on another stream (which waits on coin_ready_ev) is ordered after the build
+  HIPCHK(c, c->coin_ready_ev.create());
+  HIPCHK(c, hipEventRecord(c->coin_ready_ev.e, s));
+  return HBX_OK;
+}
+
+// The signature-share check launch at `lanes` (1 or 2) lanes per check over `grid` blocks: the
+// tiles (chunks, instances) of a matrix verification (tiles = nullptr), or the listed tiles of an
+// add, grid (T, 1) (addplan.hpp).  Shares, decode statuses, present mask and verdicts are [I][n].
+static int launch_sig_checks(hbx_ctx* c, hipStream_t s, int lanes, dim3 grid, const uint2* tiles, const g2a* sig,
+                             const int32_t* sig_st, const uint8_t* d_present, uint32_t n, uint8_t* vd) {
+  timed t_(c, HBX_K_VERIFY_SIG, s);
+  c->coin_lanes_used = lanes;
+  c->coin_tiles = grid.x * grid.y;
+  if (lanes == 2) {
+    const size_t glanes = (size_t)grid.x * grid.y * 64;
+    if (!c->gslot.ensure(glanes * 2 * LDS_FQ6D_PACKED * 4))
+      return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_verify_sig_shares: out of device memory (slots)");
+    if (!c->fb_coin.ensure(4)) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_verify_sig_shares: out of device memory");
+    HIPCHK(c, hipMemsetAsync(c->fb_coin.p, 0, 4, s));
+    c->fb_last = &c->fb_coin;
+    // Miller loops; the final exponentiation with compressed runs; then the pairs whose
+    // decompression met g3 = 0 (SHARE_FALLBACK) once more, Miller and Granger-Scott squarings
+    // only (both launches return at once per pair when there are none)
+    for (uint32_t retry = 0; retry < 2; retry++) {
+      hipLaunchKernelGGL(k_verify_sig_shares2, grid, dim3(64), 0, s, c->coin_Hp.as<g2a>(), c->pk.as<g1a>(), c->n_keys, sig,
+                         sig_st, d_present, n, vd, c->gslot.as<uint32_t>(), retry, c->coin_lines_d.as<line_pre_d>(), tiles);
+      HIPCHK(c, hipGetLastError());
+      if (retry == 0)
+        hipLaunchKernelGGL(k_verify_sig_shares2_fe<true>, grid, dim3(64), 0, s, n, vd, c->gslot.as<uint32_t>(),
+                           c->force_fallback, c->fb_coin.as<uint32_t>(), tiles);
+      else
+        hipLaunchKernelGGL(k_verify_sig_shares2_fe<false>, grid, dim3(64), 0, s, n, vd, c->gslot.as<uint32_t>(), 0u,
+                           c->fb_coin.as<uint32_t>(), tiles);
+      HIPCHK(c, hipGetLastError());
+    }
+  } else {
+    c->fb_last = nullptr;  // the one-lane coin check has no fallback path
+    hipLaunchKernelGGL(k_verify_sig_shares, grid, dim3(64), 0, s, c->coin_lines_d.as<line_pre_d>(), c->coin_Hp.as<g2a>(),
+                       c->pk.as<g1a>(), c->n_keys, sig, sig_st, d_present, n, vd, tiles);
+    HIPCHK(c, hipGetLastError());
+  }
+  return HBX_OK;
+}
+
 // Signature-share checks of the prepared nonces on device buffers: d_sig96 [count][n][96],
 // d_present [count][n] bytes (NULL = all present); statuses in c->coin_valid.
 static int verify_sig_impl(hbx_ctx* c, const uint8_t* d_sig96, const uint8_t* d_present, uint32_t n, uint32_t count,
@@ -1975,60 +2051,13 @@ static int verify_sig_impl(hbx_ctx* c, const uint8_t* d_sig96, const uint8_t* d_
   const size_t waves1 = (size_t)((n + 63) / 64) * count;
   const int lanes = c->verify_lanes == 1 || c->verify_lanes == 2 ? c->verify_lanes
                     : waves1 < FILL_WAVES ? 2 : 1;
-  c->coin_lanes_used = lanes;
-  if (!c->coin_lines_ready) {
-    // H''s prepared lines (wave-uniform loads): the one-lane kernel's mixed loop, and since round 6
-    // the two-lane kernel's H' pair (its lanes then generate only sigma's lines, together)
-    timed t_(c, HBX_K_PREPARE_LINES, s);
-    hipLaunchKernelGGL(k_prepare_lines<true>, dim3((count * LINE_K + 63) / 64), dim3(64), 0, s, c->coin_Hp.as<g2a>(), count,
-                       c->coin_lines_d.as<line_pre_d>(), c->coin_scratch.as<fq2d>(), nullptr, 0u, nullptr, nullptr, nullptr, 1u,
-                       UINT32_MAX, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0u);
-    HIPCHK(c, hipGetLastError());
-    const uint32_t nl = count * MILLER_LINES;
-    hipLaunchKernelGGL(k_normalise_lines, dim3((nl + 63) / 64), dim3(64), 0, s, c->coin_lines.as<line_pre>(),
-                       c->coin_scratch.as<fq2d>(), nl, c->coin_lines_d.as<line_pre_d>(), nullptr, nullptr, nullptr, nullptr);
-    HIPCHK(c, hipGetLastError());
-    c->coin_lines_ready = true;
-    // the lines are built on this call's stream: move the prepare event past them, so a later
-    // one-lane check on another stream (which waits on coin_ready_ev) is ordered after the build
-    HIPCHK(c, c->coin_ready_ev.create());
-    HIPCHK(c, hipEventRecord(c->coin_ready_ev.e, s));
-  }
-  {
-    timed t_(c, HBX_K_VERIFY_SIG, s);
-    if (lanes == 2) {
-      const size_t glanes = (size_t)((n + 31) / 32) * count * 64;
-      if (!c->gslot.ensure(glanes * 2 * LDS_FQ6D_PACKED * 4))
-        return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_verify_sig_shares: out of device memory (slots)");
-      if (!c->fb_coin.ensure(4)) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_verify_sig_shares: out of device memory");
-      HIPCHK(c, hipMemsetAsync(c->fb_coin.p, 0, 4, s));
-      c->fb_last = &c->fb_coin;
-      const dim3 grid((n + 31) / 32, count);
-      // Miller loops; the final exponentiation with compressed runs; then the pairs whose
-      // decompression met g3 = 0 (SHARE_FALLBACK) once more, Miller and Granger-Scott squarings
-      // only (both launches return at once per pair when there are none)
-      for (uint32_t retry = 0; retry < 2; retry++) {
-        hipLaunchKernelGGL(k_verify_sig_shares2, grid, dim3(64), 0, s, c->coin_Hp.as<g2a>(), c->pk.as<g1a>(), c->n_keys,
-                           c->coin_sig.as<g2a>(), c->coin_sig_st.as<int32_t>(), d_present, n, c->coin_valid.as<uint8_t>(),
-                           c->gslot.as<uint32_t>(), retry, c->coin_lines_d.as<line_pre_d>());
-        HIPCHK(c, hipGetLastError());
-        if (retry == 0)
-          hipLaunchKernelGGL(k_verify_sig_shares2_fe<true>, grid, dim3(64), 0, s, n, c->coin_valid.as<uint8_t>(),
-                             c->gslot.as<uint32_t>(), c->force_fallback, c->fb_coin.as<uint32_t>());
-        else
-          hipLaunchKernelGGL(k_verify_sig_shares2_fe<false>, grid, dim3(64), 0, s, n, c->coin_valid.as<uint8_t>(),
-                             c->gslot.as<uint32_t>(), 0u, c->fb_coin.as<uint32_t>());
-        HIPCHK(c, hipGetLastError());
-      }
-    } else {
-      c->fb_last = nullptr;  // the one-lane coin check has no fallback path
-      hipLaunchKernelGGL(k_verify_sig_shares, dim3((n + 63) / 64, count), dim3(64), 0, s, c->coin_lines_d.as<line_pre_d>(),
-                         c->coin_Hp.as<g2a>(), c->pk.as<g1a>(), c->n_keys, c->coin_sig.as<g2a>(),
-                         c->coin_sig_st.as<int32_t>(), d_present, n, c->coin_valid.as<uint8_t>());
-    }
-  }
-  HIPCHK(c, hipGetLastError());
+  if (int rc = coin_prepare_lines(c, s)) return rc;
+  const uint32_t per = lanes == 2 ? 32 : 64;
+  if (int rc = launch_sig_checks(c, s, lanes, dim3((n + per - 1) / per, count), nullptr, c->coin_sig.as<g2a>(),
+                                 c->coin_sig_st.as<int32_t>(), d_present, n, c->coin_valid.as<uint8_t>()))
+    return rc;
   c->coin_n = n;
+  c->coin_live = true;
   return HBX_OK;
 }
 
@@ -2201,10 +2230,10 @@ int hbx_verify_sigs_keyed(hbx_ctx* c, const uint8_t* pk48, uint32_t nkeys, const
                            c->vs_sig_st.as<int32_t>(), m, st, c->vk_gslot.as<uint32_t>(), retry);
         if (retry == 0)
           hipLaunchKernelGGL(k_verify_sig_shares2_fe<true>, grid, dim3(64), 0, s, m, st, c->vk_gslot.as<uint32_t>(),
-                             c->force_fallback, c->fb_sigs.as<uint32_t>());
+                             c->force_fallback, c->fb_sigs.as<uint32_t>(), nullptr);
         else
           hipLaunchKernelGGL(k_verify_sig_shares2_fe<false>, grid, dim3(64), 0, s, m, st, c->vk_gslot.as<uint32_t>(), 0u,
-                             c->fb_sigs.as<uint32_t>());
+                             c->fb_sigs.as<uint32_t>(), nullptr);
       }
     }
     HIPCHK(c, hipGetLastError());
@@ -2312,11 +2341,14 @@ int hbx_bivar_check_acks(hbx_ctx* c, const uint8_t* commit48, uint32_t p, uint32
 
 // combine_signatures + master check + parity of every prepared nonce over the valid shares of
 // the last signature-share verification (masked by d_use [I][n] when given): results in
-// coin_out96 / coin_comb_st / coin_ok / coin_par.
-static int combine_sigs_impl(hbx_ctx* c, const uint8_t* master_pk48, uint32_t t, const uint8_t* d_use, hipStream_t s) {
+// coin_out96 / coin_comb_st / coin_ok / coin_par.  d_insts (device, `rows` entries): the listed
+// instances only, block b = instance d_insts[b]; no other entry of the four results is written.
+static int combine_sigs_impl(hbx_ctx* c, const uint8_t* master_pk48, uint32_t t, const uint8_t* d_use, hipStream_t s,
+                             const uint32_t* d_insts = nullptr, uint32_t rows = 0) {
   if (!master_pk48 || t == 0 || t > (uint32_t)COMBINE_MAX_T) return fail(c, HBX_E_INVALID_ARG, "hbx_combine_signatures: bad args");
   if (c->coin_n == 0) return fail(c, HBX_E_NO_CIPHERTEXTS, "no verified signature shares");
   const uint32_t I = c->coin_I;
+  if (!d_insts) rows = I;
   const size_t m = (size_t)I * c->coin_n;
   if (!c->coin_comb.ensure((size_t)I * sizeof(g2a)) || !c->coin_comb_st.ensure((size_t)I * 4) ||
       !c->coin_mpk_comp.ensure(48) || !c->coin_mpk.ensure(sizeof(g1a)) || !c->coin_mpk_st.ensure(4) ||
@@ -2339,7 +2371,8 @@ static int combine_sigs_impl(hbx_ctx* c, const uint8_t* master_pk48, uint32_t t,
   }
   const uint8_t* valid = c->coin_valid.as<uint8_t>();
   if (d_use) {
-    hipLaunchKernelGGL(k_coin_use, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, valid, d_use, m,
+    const size_t mr = (size_t)rows * c->coin_n;
+    hipLaunchKernelGGL(k_coin_use, dim3((unsigned)((mr + 255) / 256)), dim3(256), 0, s, valid, d_use, c->coin_n, mr, d_insts,
                        c->coin_use.as<uint8_t>());
     HIPCHK(c, hipGetLastError());
     valid = c->coin_use.as<uint8_t>();
@@ -2347,14 +2380,14 @@ static int combine_sigs_impl(hbx_ctx* c, const uint8_t* master_pk48, uint32_t t,
   {
     // the G2 combine (waves 0..2) and the master-key identity (wave 3), one block per instance
     timed t_(c, HBX_K_COMBINE_SIGS, s);
-    hipLaunchKernelGGL(k_combine_sigs, dim3(I), dim3(SIGCOMB_THREADS), 0, s, valid, c->coin_sig.as<g2a>(), c->coin_n, t,
+    hipLaunchKernelGGL(k_combine_sigs, dim3(rows), dim3(SIGCOMB_THREADS), 0, s, valid, c->coin_sig.as<g2a>(), c->coin_n, t,
                        c->pk.as<g1a>(), c->pk64.as<g1a>(), c->coin_mpk.as<g1a>(), c->coin_comb.as<g2a>(),
                        c->coin_comb_st.as<int32_t>(), c->coin_ok.as<uint8_t>(),
-                       c->g1tab.p ? c->g1tab.as<g1a>() : nullptr);
+                       c->g1tab.p ? c->g1tab.as<g1a>() : nullptr, d_insts);
   }
   HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(k_sig_parity, dim3((I + 63) / 64), dim3(64), 0, s, c->coin_comb.as<g2a>(), c->coin_comb_st.as<int32_t>(),
-                     I, c->coin_par.as<uint8_t>(), c->coin_out96.as<uint8_t>());
+  hipLaunchKernelGGL(k_sig_parity, dim3((rows + 63) / 64), dim3(64), 0, s, c->coin_comb.as<g2a>(),
+                     c->coin_comb_st.as<int32_t>(), rows, c->coin_par.as<uint8_t>(), c->coin_out96.as<uint8_t>(), d_insts);
   HIPCHK(c, hipGetLastError());
   return HBX_OK;
 }
@@ -2388,6 +2421,176 @@ int hbx_combine_signatures_d(hbx_ctx* c, const uint8_t* master_pk48, uint32_t t,
   if (d_status) HIPCHK(c, hipMemcpyAsync(d_status, c->coin_comb_st.p, (size_t)I * 4, hipMemcpyDeviceToDevice, s));
   if (d_master_ok) HIPCHK(c, hipMemcpyAsync(d_master_ok, c->coin_ok.p, I, hipMemcpyDeviceToDevice, s));
   if (d_parity) HIPCHK(c, hipMemcpyAsync(d_parity, c->coin_par.p, I, hipMemcpyDeviceToDevice, s));
+  return HBX_OK;
+}
+
+// ---- Common Coin, incremental (include/hbx.h) -------------------------------------------------
+static_assert(hbx_addplan::SHAPE_SENDERS[0] == 64 && hbx_addplan::SHAPE_SENDERS[1] == 32,
+              "addplan.hpp and the coin check kernels disagree on a tile's shape");
+
+int hbx_add_sig_shares_d(hbx_ctx* c, const uint8_t* d_sig96, const uint32_t* inst, const uint32_t* sender, uint32_t count,
+                         uint32_t n, uint8_t* d_status, void* stream) {
+  if (!c || n == 0 || (count && (!d_sig96 || !inst || !sender)))
+    return fail(c, HBX_E_INVALID_ARG, "hbx_add_sig_shares_d: bad args");
+  if (c->n_keys == 0) return fail(c, HBX_E_NO_KEYS, "hbx_set_pk_shares has not been called");
+  if (c->coin_I == 0) return fail(c, HBX_E_NO_CIPHERTEXTS, "hbx_add_sig_shares_d: hbx_prepare_nonces has not been called");
+  const uint32_t I = c->coin_I;
+  if (c->coin_live && n != c->coin_n)
+    return fail(c, HBX_E_INVALID_ARG, "hbx_add_sig_shares_d: n=%u but the round's matrix has n=%u", n, c->coin_n);
+  hbx_addplan::plan pl;
+  switch (hbx_addplan::build(inst, sender, count, n, I, UINT32_MAX, pl)) {
+    case hbx_addplan::PLAN_BAD_PROPOSER:
+      return fail(c, HBX_E_INVALID_ARG, "hbx_add_sig_shares_d: an instance index >= %u prepared nonces", I);
+    case hbx_addplan::PLAN_DUPLICATE:
+      return fail(c, HBX_E_INVALID_ARG, "hbx_add_sig_shares_d: the same (instance, sender) twice in one call");
+    default:
+      break;
+  }
+  HBX_ENTER(c, stream);
+  const size_t m = (size_t)n * I;
+  if (!c->coin_sig.ensure(m * sizeof(g2a)) || !c->coin_sig_st.ensure(m * 4) || !c->coin_valid.ensure(m))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_add_sig_shares_d: out of device memory");
+  if (c->coin_ready_ev.e) HIPCHK(c, hipStreamWaitEvent(s, c->coin_ready_ev.e, 0));  // the nonces' hashes are in
+  if (!c->coin_live) {
+    // no share has arrived: every entry absent, none decoded (no pairing work)
+    HIPCHK(c, hipMemsetAsync(c->coin_valid.p, HBX_SHARE_ABSENT, m, s));
+    HIPCHK(c, hipMemsetAsync(c->coin_sig_st.p, 0xFF, m * 4, s));
+    c->coin_n = n;
+    c->coin_live = true;
+  }
+  if (count == 0) return HBX_OK;
+  if (!c->coin_add_sig.ensure(m * sizeof(g2a)) || !c->coin_add_st.ensure(m * 4) || !c->coin_add_valid.ensure(m) ||
+      !c->coin_add_mask.ensure(m) || !c->coin_add_ist.ensure(count))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_add_sig_shares_d: out of device memory");
+  if (c->coin_add_mask_m < m) {  // a new buffer, or one an interrupted call left marked
+    HIPCHK(c, hipMemsetAsync(c->coin_add_mask.p, 0, c->coin_add_mask.cap, s));
+  }
+  c->coin_add_mask_m = 0;
+  // lanes per check from what is live: the matrix call's rule over the touched one-lane tiles
+  const int lanes = c->verify_lanes == 1 || c->verify_lanes == 2 ? c->verify_lanes
+                    : pl.tiles[0].size() < FILL_WAVES ? 2 : 1;
+  const std::vector<hbx_addplan::tile>& tiles = pl.tiles[hbx_addplan::shape_of_lanes(lanes)];
+  // the items and the tile list, consumed before the call returns (pinned staging, one upload)
+  const size_t items_bytes = (size_t)count * sizeof(uint2), tiles_bytes = tiles.size() * sizeof(uint2);
+  uint8_t* pin = staging_begin(c, items_bytes + tiles_bytes);
+  if (!pin) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_add_sig_shares_d: out of memory (staging)");
+  uint2* it = reinterpret_cast<uint2*>(pin);
+  for (uint32_t k = 0; k < count; k++) it[k] = make_uint2(inst[k], sender[k]);
+  if (tiles_bytes) memcpy(pin + items_bytes, tiles.data(), tiles_bytes);
+  if (int rc = staging_upload(c, items_bytes + tiles_bytes, s)) return rc;
+  const uint2* d_items = c->rg_dev.as<uint2>();
+  const uint2* d_tiles = reinterpret_cast<const uint2*>(c->rg_dev.as<uint8_t>() + items_bytes);
+  {
+    timed t_(c, HBX_K_DECODE_SIGS, s);
+    hipLaunchKernelGGL(k_coin_add_decode, dim3((count + 63) / 64), dim3(64), 0, s, d_sig96, d_items, count, n,
+                       c->coin_add_sig.as<g2a>(), c->coin_add_st.as<int32_t>(), c->coin_add_mask.as<uint8_t>(),
+                       c->coin_add_ist.as<uint8_t>());
+  }
+  HIPCHK(c, hipGetLastError());
+  if (pl.live) {
+    if (int rc = coin_prepare_lines(c, s)) return rc;
+    if (int rc = launch_sig_checks(c, s, lanes, dim3((unsigned)tiles.size(), 1), d_tiles, c->coin_add_sig.as<g2a>(),
+                                   c->coin_add_st.as<int32_t>(), c->coin_add_mask.as<uint8_t>(), n,
+                                   c->coin_add_valid.as<uint8_t>()))
+      return rc;
+  } else {
+    c->coin_tiles = 0;
+    c->fb_last = nullptr;
+  }
+  hipLaunchKernelGGL(k_coin_add_merge, dim3((count + 255) / 256), dim3(256), 0, s, d_items, count, n,
+                     c->coin_add_sig.as<g2a>(), c->coin_add_st.as<int32_t>(), c->coin_add_valid.as<uint8_t>(),
+                     c->coin_add_mask.as<uint8_t>(), c->coin_add_ist.as<uint8_t>(), c->coin_sig.as<g2a>(),
+                     c->coin_sig_st.as<int32_t>(), c->coin_valid.as<uint8_t>(), d_status);
+  HIPCHK(c, hipGetLastError());
+  c->coin_add_mask_m = c->coin_add_mask.cap;
+  return HBX_OK;
+}
+
+int hbx_add_sig_shares(hbx_ctx* c, const uint8_t* sig96, const uint32_t* inst, const uint32_t* sender, uint32_t count,
+                       uint32_t n, uint8_t* status) {
+  if (!c || n == 0 || (count && (!sig96 || !inst || !sender)))
+    return fail(c, HBX_E_INVALID_ARG, "hbx_add_sig_shares: bad args");
+  HBX_ENTER(c, c->stream);
+  if (!c->coin_add_sig96.ensure((size_t)count * 96) || !c->coin_add_dst.ensure(count))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_add_sig_shares: out of device memory");
+  if (count) HIPCHK(c, hipMemcpyAsync(c->coin_add_sig96.p, sig96, (size_t)count * 96, hipMemcpyHostToDevice, c->stream));
+  int rc = hbx_add_sig_shares_d(c, c->coin_add_sig96.as<uint8_t>(), inst, sender, count, n, c->coin_add_dst.as<uint8_t>(),
+                                c->stream);
+  if (rc) return rc;
+  std::vector<uint8_t> st(count);
+  if (count) HIPCHK(c, hipMemcpyAsync(st.data(), c->coin_add_dst.p, count, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (status && count) memcpy(status, st.data(), count);
+  return HBX_OK;
+}
+
+uint32_t hbx_get_coin_tiles_used(const hbx_ctx* c) { return c ? c->coin_tiles : 0; }
+
+// The listed instances must be prepared ones, each once (before anything is launched).
+static int coin_insts_check(hbx_ctx* c, const char* fn, const uint32_t* insts, uint32_t ninsts) {
+  std::vector<uint8_t> seen(c->coin_I, 0);
+  for (uint32_t k = 0; k < ninsts; k++) {
+    if (insts[k] >= c->coin_I || seen[insts[k]])
+      return fail(c, HBX_E_INVALID_ARG, "%s: insts[%u] = %u is %s", fn, k, insts[k],
+                  insts[k] >= c->coin_I ? "not a prepared instance" : "listed twice");
+    seen[insts[k]] = 1;
+  }
+  return HBX_OK;
+}
+
+int hbx_combine_signatures_insts_d(hbx_ctx* c, const uint8_t* master_pk48, uint32_t t, const uint32_t* insts,
+                                   uint32_t ninsts, const uint8_t* d_use, uint8_t* d_sig96, int32_t* d_status,
+                                   uint8_t* d_master_ok, uint8_t* d_parity, void* stream) {
+  if (!c || (!insts && ninsts)) return fail(c, HBX_E_INVALID_ARG, "hbx_combine_signatures_insts_d: bad args");
+  if (int rc = coin_insts_check(c, "hbx_combine_signatures_insts_d", insts, ninsts)) return rc;
+  if (ninsts == 0) return HBX_OK;
+  HBX_ENTER(c, stream);
+  // the listed instances, consumed before the call returns (pinned staging, as an add's items)
+  uint8_t* pin = staging_begin(c, (size_t)ninsts * 4);
+  if (!pin) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_combine_signatures_insts_d: out of memory (staging)");
+  memcpy(pin, insts, (size_t)ninsts * 4);
+  if (int rc = staging_upload(c, (size_t)ninsts * 4, s)) return rc;
+  const uint32_t* d_insts = c->rg_dev.as<uint32_t>();
+  if (int rc = combine_sigs_impl(c, master_pk48, t, d_use, s, d_insts, ninsts)) return rc;
+  if (d_sig96 || d_status || d_master_ok || d_parity) {
+    hipLaunchKernelGGL(k_coin_scatter, dim3((ninsts * 96 + 255) / 256), dim3(256), 0, s, d_insts, ninsts,
+                       c->coin_out96.as<uint8_t>(), c->coin_comb_st.as<int32_t>(), c->coin_ok.as<uint8_t>(),
+                       c->coin_par.as<uint8_t>(), d_sig96, d_status, d_master_ok, d_parity);
+    HIPCHK(c, hipGetLastError());
+  }
+  return HBX_OK;
+}
+
+int hbx_combine_signatures_insts(hbx_ctx* c, const uint8_t* master_pk48, uint32_t t, const uint32_t* insts, uint32_t ninsts,
+                                 const uint8_t* use, uint8_t* sig96, int32_t* status, uint8_t* master_ok, uint8_t* parity) {
+  if (!c || (!insts && ninsts)) return fail(c, HBX_E_INVALID_ARG, "hbx_combine_signatures_insts: bad args");
+  if (int rc = coin_insts_check(c, "hbx_combine_signatures_insts", insts, ninsts)) return rc;
+  if (ninsts == 0) return HBX_OK;
+  HBX_ENTER(c, c->stream);
+  const uint32_t I = c->coin_I;
+  const size_t m = (size_t)I * c->coin_n;
+  if (use && m) {
+    if (!c->coin_use_in.ensure(m)) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_combine_signatures_insts: out of device memory");
+    HIPCHK(c, hipMemcpyAsync(c->coin_use_in.p, use, m, hipMemcpyHostToDevice, s));
+  }
+  if (int rc = hbx_combine_signatures_insts_d(c, master_pk48, t, insts, ninsts, use && m ? c->coin_use_in.as<uint8_t>() : nullptr,
+                                              nullptr, nullptr, nullptr, nullptr, s))
+    return rc;
+  std::vector<uint8_t> out(sig96 ? (size_t)I * 96 : 0), ok(I), par(I);
+  std::vector<int32_t> st(I);
+  if (sig96) HIPCHK(c, hipMemcpyAsync(out.data(), c->coin_out96.p, (size_t)I * 96, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(ok.data(), c->coin_ok.p, I, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(par.data(), c->coin_par.p, I, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(st.data(), c->coin_comb_st.p, (size_t)I * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  // the listed instances' entries only: nothing else of the caller's arrays is written
+  for (uint32_t k = 0; k < ninsts; k++) {
+    const uint32_t j = insts[k];
+    if (sig96) memcpy(sig96 + (size_t)j * 96, out.data() + (size_t)j * 96, 96);
+    if (status) status[j] = st[j];
+    if (master_ok) master_ok[j] = ok[j];
+    if (parity) parity[j] = par[j];
+  }
   return HBX_OK;
 }
 
@@ -2954,10 +3157,10 @@ int hbx_sk_decrypt(hbx_ctx* c, const uint8_t* sk32, const uint8_t* u48, const ui
                            c->dec_st.as<int32_t>(), m, st, c->gslot.as<uint32_t>(), retry);
         if (retry == 0)
           hipLaunchKernelGGL(k_verify_sig_shares2_fe<true>, grid, dim3(64), 0, s, m, st, c->gslot.as<uint32_t>(),
-                             c->force_fallback, c->fb_ct.as<uint32_t>());
+                             c->force_fallback, c->fb_ct.as<uint32_t>(), nullptr);
         else
           hipLaunchKernelGGL(k_verify_sig_shares2_fe<false>, grid, dim3(64), 0, s, m, st, c->gslot.as<uint32_t>(), 0u,
-                             c->fb_ct.as<uint32_t>());
+                             c->fb_ct.as<uint32_t>(), nullptr);
       }
     } else {
       rc = prepare_impl(c, c->u_comp_own.as<uint8_t>() + (size_t)j0 * 48, c->v_blob_own.as<uint8_t>(),

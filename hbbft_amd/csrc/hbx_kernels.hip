@@ -653,12 +653,14 @@ __global__ void __launch_bounds__(64) k_verify_sig_shares2(const g2a* __restrict
                                                            const int32_t* __restrict__ sig_status,
                                                            const uint8_t* __restrict__ present, uint32_t n,
                                                            uint8_t* __restrict__ valid, uint32_t* __restrict__ gslot,
-                                                           uint32_t retry, const line_pre_d* __restrict__ Hlines) {
+                                                           uint32_t retry, const line_pre_d* __restrict__ Hlines,
+                                                           const uint2* __restrict__ tiles) {
   __shared__ uint32_t region[LDS2_DWORDS * 64];
   const int lane = (int)(threadIdx.x & 63);
   const bool l1 = (lane & 1) != 0;
-  const uint32_t i = blockIdx.x * 32 + (uint32_t)(lane >> 1);
-  const uint32_t inst = blockIdx.y;
+  const uint2 tl = share_tile(tiles);  // (sender chunk, instance); hbx_add_sig_shares_d lists its tiles
+  const uint32_t i = tl.x * 32 + (uint32_t)(lane >> 1);
+  const uint32_t inst = tl.y;
   if (i >= n) return;  // whole pairs
   const size_t idx = (size_t)inst * n + i;
   // retry: only the pairs k_verify_sig_shares2_fe<true> sent back (SHARE_FALLBACK), Miller again
@@ -667,8 +669,9 @@ __global__ void __launch_bounds__(64) k_verify_sig_shares2(const g2a* __restrict
   bool tf = true;
   if (res == HBX_SHARE_VALID) {
     // lane 0: e(pk_i, H'); lane 1: e(-[m] g1, sigma_i)  (H' = [m] H: the same verdict)
+    // (the point itself is read where it is used, after the loop: held from here it kept 48 more
+    // registers live across the Miller loop, 123 spilled VGPRs against 55)
     const g2a* qp = l1 ? sig + idx : H + inst;
-    const g2a Q = *qp;
     g1a P;
     if (l1) {
       P.x = fq_from_const(G1_MGEN_X);
@@ -677,7 +680,7 @@ __global__ void __launch_bounds__(64) k_verify_sig_shares2(const g2a* __restrict
     } else {
       P = pk[i];
     }
-    const bool use = !(Q.inf || P.inf);  // a pairing with the identity contributes 1
+    const bool use = !(qp->inf || P.inf);  // a pairing with the identity contributes 1
     lds_u32* reg = (lds_u32*)region;
     const int pl = lane & ~1;
     g2jd T;
@@ -695,7 +698,7 @@ __global__ void __launch_bounds__(64) k_verify_sig_shares2(const g2a* __restrict
       f = miller_gen2d(qp, fqd_from_fq(P.x), fqd_from_fq(P.y), use, l1, (lds2)(reg + lane), reg + pl, T);
     }
     // sigma's membership in G2 from lane 1's T = [|x|] sigma (decode skipped it); lane 0's is H's
-    tf = !l1 || g2_torsion_free_from_T(T, Q);
+    tf = !l1 || g2_torsion_free_from_T(T, *qp);
     // this lane's half of f_A f_B to the pair's global slot
     uint32_t* gb = gslot + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (2 * LDS_FQ6D_PACKED * 64) + pl;
     slot_put_fq6d(gb + (l1 ? 1 : 0), 64u, fq6d_reduce(f));
@@ -714,13 +717,15 @@ __global__ void __launch_bounds__(64) k_verify_sig_shares2(const g2a* __restrict
 template <bool KARA>
 __global__ void __launch_bounds__(64) k_verify_sig_shares2_fe(uint32_t n, uint8_t* __restrict__ valid,
                                                               uint32_t* __restrict__ gslot, uint32_t force_fallback,
-                                                              uint32_t* __restrict__ fb) {
+                                                              uint32_t* __restrict__ fb,
+                                                              const uint2* __restrict__ tiles) {
   __shared__ uint32_t region[LDS2_DWORDS * 64];
   const int lane = (int)(threadIdx.x & 63);
   const bool l1 = (lane & 1) != 0;
-  const uint32_t i = blockIdx.x * 32 + (uint32_t)(lane >> 1);
+  const uint2 tl = share_tile(tiles);
+  const uint32_t i = tl.x * 32 + (uint32_t)(lane >> 1);
   if (i >= n) return;
-  const size_t idx = (size_t)blockIdx.y * n + i;
+  const size_t idx = (size_t)tl.y * n + i;
   if (valid[idx] != SHARE_PENDING) return;  // pair-uniform
   lds_u32* reg = (lds_u32*)region;
   const int pl = lane & ~1;
@@ -742,8 +747,8 @@ __global__ void __launch_bounds__(64) k_verify_sig_shares2_fe(uint32_t n, uint8_
     }
   }
 }
-template __global__ void k_verify_sig_shares2_fe<true>(uint32_t, uint8_t*, uint32_t*, uint32_t, uint32_t*);
-template __global__ void k_verify_sig_shares2_fe<false>(uint32_t, uint8_t*, uint32_t*, uint32_t, uint32_t*);
+template __global__ void k_verify_sig_shares2_fe<true>(uint32_t, uint8_t*, uint32_t*, uint32_t, uint32_t*, const uint2*);
+template __global__ void k_verify_sig_shares2_fe<false>(uint32_t, uint8_t*, uint32_t*, uint32_t, uint32_t*, const uint2*);
 
 // Ciphertext::verify on a lane pair (hbx_sk_decrypt in HBX_CT_CHECK_PAIR mode): e(U_j, H'_j) e(-[m] g1, W_j)
 // == 1 with H' = [m] H (k_prepare_ct), so the verdict is the reference's e(g1, W) == e(U, H).  Both G2
@@ -1941,12 +1946,89 @@ __global__ void __launch_bounds__(64) k_scatter_cols(const int32_t* __restrict__
 // ----------------------------------------------------------------------------------------------
 #if HBX_IN_TU(5)
 // combine_signatures over a caller-chosen subset of the verified shares (the shares a node held
-// when try_output ran, common_coin.rs:163-190): out[k] = valid[k] where use[k], else ABSENT
+// when try_output ran, common_coin.rs:163-190): out[k] = valid[k] where use[k], else ABSENT.
+// m = rows * n entries: every instance's row (insts = nullptr), or the rows of the listed instances
+// only (hbx_combine_signatures_insts_d: row b of the launch is instance insts[b]).
 __global__ void __launch_bounds__(256) k_coin_use(const uint8_t* __restrict__ valid, const uint8_t* __restrict__ use,
-                                                  size_t m, uint8_t* __restrict__ out) {
-  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+                                                  uint32_t n, size_t m, const uint32_t* __restrict__ insts,
+                                                  uint8_t* __restrict__ out) {
+  size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= m) return;
+  if (insts) k = (size_t)insts[k / n] * n + k % n;
   out[k] = use[k] ? valid[k] : (uint8_t)HBX_SHARE_ABSENT;
+}
+
+// hbx_add_sig_shares_d, decode: one lane per item (x = instance, y = sender), the matrix call's
+// decode (k_decompress_g2 without the subgroup test: the check kernels take G2 membership from their
+// Miller loop) into the add's candidate matrix at (instance, sender); the item's position is set in
+// `mask`, the present mask of the add's tile launch.  An item of a sender >= n touches no position
+// and meets no check kernel, so its decode runs the subgroup test itself: item_st[k] is what the
+// reference would see, a message serde rejects (UNDECODABLE) or Err(UnknownSender)
+// (common_coin.rs:158).
+__global__ void __launch_bounds__(64) k_coin_add_decode(const uint8_t* __restrict__ sig96, const uint2* __restrict__ items,
+                                                        uint32_t count, uint32_t n, g2a* __restrict__ sig_c,
+                                                        int32_t* __restrict__ status_c, uint8_t* __restrict__ mask,
+                                                        uint8_t* __restrict__ item_st) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= count) return;
+  const uint2 it = items[k];
+  g2a p;
+  int32_t st = g2_decompress(sig96 + (size_t)k * 96, p);
+  if (it.y >= n) {
+    if (st == HBX_PT_OK && !g2_is_torsion_free(p)) st = HBX_PT_NOT_IN_SUBGROUP;
+    item_st[k] = st == HBX_PT_OK || st == HBX_PT_INFINITY ? HBX_SHARE_UNKNOWN_SENDER : HBX_SHARE_UNDECODABLE;
+    return;
+  }
+  const size_t idx = (size_t)it.x * n + it.y;
+  status_c[idx] = st;
+  sig_c[idx] = p;
+  mask[idx] = 1;
+}
+
+// hbx_add_sig_shares_d, merge: the candidate's verdict is the item's status.  A VALID entry stays
+// when the candidate is not VALID (the reference returns the fault before `insert`,
+// common_coin.rs:151-155); otherwise the entry takes the candidate's status, and its point where it
+// decoded (`insert` replaces, :156).  The candidate matrix is apart from the round's, so a kept
+// entry was never displaced.  Clears the item's mask byte.
+__global__ void __launch_bounds__(256) k_coin_add_merge(const uint2* __restrict__ items, uint32_t count, uint32_t n,
+                                                        const g2a* __restrict__ sig_c, const int32_t* __restrict__ status_c,
+                                                        const uint8_t* __restrict__ valid_c, uint8_t* __restrict__ mask,
+                                                        const uint8_t* __restrict__ item_st, g2a* __restrict__ sig,
+                                                        int32_t* __restrict__ sig_status, uint8_t* __restrict__ valid,
+                                                        uint8_t* __restrict__ d_status) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= count) return;
+  const uint2 it = items[k];
+  if (it.y >= n) {
+    if (d_status) d_status[k] = item_st[k];
+    return;
+  }
+  const size_t idx = (size_t)it.x * n + it.y;
+  const uint8_t v = valid_c[idx];
+  mask[idx] = 0;
+  if (d_status) d_status[k] = v;
+  if (valid[idx] == HBX_SHARE_VALID && v != HBX_SHARE_VALID) return;
+  const int32_t st = status_c[idx];
+  valid[idx] = v;
+  sig_status[idx] = st;
+  if (st == HBX_PT_OK || st == HBX_PT_INFINITY) sig[idx] = sig_c[idx];
+}
+
+// hbx_combine_signatures_insts_d: the listed instances' results into the caller's arrays (each may
+// be nullptr), one lane per byte of a compressed signature; no other entry is written
+__global__ void __launch_bounds__(256) k_coin_scatter(const uint32_t* __restrict__ insts, uint32_t ninsts,
+                                                      const uint8_t* __restrict__ out96, const int32_t* __restrict__ st,
+                                                      const uint8_t* __restrict__ ok, const uint8_t* __restrict__ par,
+                                                      uint8_t* __restrict__ d_sig96, int32_t* __restrict__ d_status,
+                                                      uint8_t* __restrict__ d_ok, uint8_t* __restrict__ d_par) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= ninsts * 96u) return;
+  const uint32_t inst = insts[k / 96u], q = k % 96u;
+  if (d_sig96) d_sig96[(size_t)inst * 96 + q] = out96[(size_t)inst * 96 + q];
+  if (q != 0) return;
+  if (d_status) d_status[inst] = st[inst];
+  if (d_ok) d_ok[inst] = ok[inst];
+  if (d_par) d_par[inst] = par[inst];
 }
 // H_i = hash_g2(nonce_i) (threshold_crypto; the nonce of agreement/mod.rs:155-165), one HASH_K-lane
 // group each.  full = 0: H'_i = h_eff P = [m] H_i (m = 3(x^2 - 1), the decryption checks' trick,
@@ -2015,10 +2097,11 @@ __global__ void __launch_bounds__(64) k_verify_sig_shares(const line_pre_d* __re
                                                           const g2a* __restrict__ sig,
                                                           const int32_t* __restrict__ sig_status,
                                                           const uint8_t* __restrict__ present, uint32_t n,
-                                                          uint8_t* __restrict__ valid) {
+                                                          uint8_t* __restrict__ valid, const uint2* __restrict__ tiles) {
   __shared__ uint32_t gslots[LDS_FQ12D_DWORDS * LDS_FQ12_STRIDE];  // final-exp base, one slot per lane
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t inst = blockIdx.y;
+  const uint2 tl = share_tile(tiles);  // (sender chunk, instance); hbx_add_sig_shares_d lists its tiles
+  const uint32_t i = tl.x * blockDim.x + threadIdx.x;
+  const uint32_t inst = tl.y;
   if (i >= n) return;
   const size_t idx = (size_t)inst * n + i;
   uint8_t res = share_precheck(sig_status[idx], present == nullptr || present[idx], i < n_keys, true);
@@ -2156,7 +2239,8 @@ __global__ void __launch_bounds__(SIGCOMB_THREADS) k_combine_sigs(const uint8_t*
                                                                   const g1a* __restrict__ master_pk,
                                                                   g2a* __restrict__ out, int32_t* __restrict__ status,
                                                                   uint8_t* __restrict__ master_ok,
-                                                                  const g1a* __restrict__ g1tab) {
+                                                                  const g1a* __restrict__ g1tab,
+                                                                  const uint32_t* __restrict__ insts) {
   // One block per instance: waves 0..2 the G2 combine (four psi-digit lanes per share), wave 3 the
   // G1 master identity (64 fixed-base window lanes).  At t = 43 that is 172 G2 tasks on 192 lanes
   // in ONE round of blocks, one wave per SIMD.  (Lane pairs splitting every Fq2 product, g2d.hpp
@@ -2167,7 +2251,8 @@ __global__ void __launch_bounds__(SIGCOMB_THREADS) k_combine_sigs(const uint8_t*
   __shared__ int s_count;
   __shared__ g2j red2[G2_THREADS / 64];
   __shared__ fr lam_s[COMBINE_LDS_T];  // lambda_k, once per share (t <= COMBINE_LDS_T)
-  const uint32_t inst = blockIdx.x;
+  // every instance, or block b the listed instance insts[b] (hbx_combine_signatures_insts_d)
+  const uint32_t inst = insts ? insts[blockIdx.x] : blockIdx.x;
   const int tid = threadIdx.x;
   const bool g1_part = tid >= G2_THREADS;  // the last wave
   if (tid == 0) {
@@ -2260,12 +2345,14 @@ __global__ void __launch_bounds__(SIGCOMB_THREADS) k_combine_sigs(const uint8_t*
   }
 }
 
-// B4 Signature::parity (common_coin.rs:173) and the compressed signature, one lane per instance.
+// B4 Signature::parity (common_coin.rs:173) and the compressed signature, one lane per instance
+// (lane b the listed instance insts[b] when a list is given).
 __global__ void __launch_bounds__(64) k_sig_parity(const g2a* __restrict__ sig, const int32_t* __restrict__ status,
                                                    uint32_t count, uint8_t* __restrict__ parity,
-                                                   uint8_t* __restrict__ sig96) {
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+                                                   uint8_t* __restrict__ sig96, const uint32_t* __restrict__ insts) {
+  uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= count) return;
+  if (insts) j = insts[j];
   if (status[j] != 0) {
     parity[j] = 0;
     for (int q = 0; q < 96; q++) sig96[(size_t)j * 96 + q] = 0;

@@ -116,6 +116,11 @@ EXPORTS = (
     "hbx_combine_decrypt_cols",
     "hbx_get_verify_tiles_used",
     "hbx_debug_live_buffers",
+    "hbx_add_sig_shares_d",
+    "hbx_add_sig_shares",
+    "hbx_combine_signatures_insts_d",
+    "hbx_combine_signatures_insts",
+    "hbx_get_coin_tiles_used",
 )
 
 DIGEST_SHA256 = 0
@@ -292,6 +297,16 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.hbx_combine_decrypt_cols.argtypes = [P, u32, u32p, u32, u8p, i32p]
         lib.hbx_get_verify_tiles_used.argtypes = [P]
         lib.hbx_get_verify_tiles_used.restype = u32
+    # the coin's incremental calls: absent from a library built before them (tools/bench_coin_incremental.py
+    # --lib times such a build through the masked matrix call)
+    if hasattr(lib, "hbx_add_sig_shares_d"):
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        lib.hbx_add_sig_shares_d.argtypes = [P, P, u32p, u32p, u32, u32, P, P]
+        lib.hbx_add_sig_shares.argtypes = [P, u8p, u32p, u32p, u32, u32, u8p]
+        lib.hbx_combine_signatures_insts_d.argtypes = [P, u8p, u32, u32p, u32, P, P, P, P, P, P]
+        lib.hbx_combine_signatures_insts.argtypes = [P, u8p, u32, u32p, u32, u8p, u8p, i32p, u8p, u8p]
+        lib.hbx_get_coin_tiles_used.argtypes = [P]
+        lib.hbx_get_coin_tiles_used.restype = u32
     # the live-allocation count: absent from a library built before it
     if hasattr(lib, "hbx_debug_live_buffers"):
         lib.hbx_debug_live_buffers.argtypes = []
@@ -749,6 +764,118 @@ class Context:
         self._check(self.lib.hbx_combine_signatures(self.h, _u8(mpk), t, _u8(sig),
                                                     st.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _u8(ok), _u8(par)))
         return sig, st, unpack_bits(ok, count), unpack_bits(par, count)
+
+    # -- common coin, incremental ------------------------------------------------------------------
+    @staticmethod
+    def _coin_items(what: str, inst, sender, count: int, n: int):
+        """The (inst, sender) index arrays of a coin add as contiguous uint32[count]."""
+        out = []
+        for name, a in (("inst", inst), ("sender", sender)):
+            a = np.asarray(a)
+            if a.ndim != 1 or a.shape[0] != count:
+                raise ValueError(f"{what}: {name} must have one entry per share ({count}), not shape {a.shape}")
+            if a.size and (a.dtype.kind not in "iu" or int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+                raise ValueError(f"{what}: {name} must hold instance / node indices (uint32)")
+            out.append(np.ascontiguousarray(a, dtype=np.uint32))
+        if not isinstance(n, (int, np.integer)) or n <= 0:
+            raise ValueError(f"{what}: n must be the number of nodes")
+        return out
+
+    @staticmethod
+    def _coin_insts(what: str, insts):
+        """The instance list of a listed combine as contiguous uint32[ninsts], each listed once."""
+        insts = np.asarray(insts)
+        if insts.ndim != 1 or (insts.size and (insts.dtype.kind not in "iu" or int(insts.min()) < 0
+                                               or int(insts.max()) > 0xFFFFFFFF)):
+            raise ValueError(f"{what}: insts must be a list of coin instances")
+        if len(set(insts.tolist())) != insts.size:
+            raise ValueError(f"{what}: an instance is listed twice")
+        return np.ascontiguousarray(insts, dtype=np.uint32)
+
+    def add_sig_shares(self, sig96, inst, sender, n: int) -> np.ndarray:
+        """hbx_add_sig_shares: the signature shares that arrived since the last call, verified and
+        merged into the round's matrix.  sig96 uint8[count, 96], inst (< prepared nonces) and sender
+        (node index) one entry each -> HBX_SHARE_* uint8[count]."""
+        sig96 = np.asarray(sig96)
+        if sig96.dtype != np.uint8 or sig96.ndim != 2 or sig96.shape[1] != 96:
+            raise ValueError(f"add_sig_shares: sig96 must be uint8[count, 96], not {sig96.dtype}{sig96.shape}")
+        sig96 = np.ascontiguousarray(sig96)
+        count = sig96.shape[0]
+        ins, snd = self._coin_items("add_sig_shares", inst, sender, count, n)
+        out = np.zeros(count, dtype=np.uint8)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        self._check(self.lib.hbx_add_sig_shares(
+            self.h, _u8(sig96) if count else None, ins.ctypes.data_as(u32p) if count else None,
+            snd.ctypes.data_as(u32p) if count else None, count, int(n), _u8(out) if count else None))
+        return out
+
+    def add_sig_shares_d(self, d_sig96, inst, sender, n: int, d_status=None, stream=None):
+        """hbx_add_sig_shares_d: d_sig96 a device uint8[count, 96] tensor (None with no items), inst /
+        sender host index arrays, d_status an optional device uint8[count]."""
+        count = 0 if d_sig96 is None else int(d_sig96.shape[0])
+        if d_sig96 is not None and (d_sig96.dim() != 2 or d_sig96.shape[1] != 96 or d_sig96.element_size() != 1
+                                    or not d_sig96.is_contiguous()):
+            raise ValueError(f"add_sig_shares_d: d_sig96 must be contiguous uint8[count, 96], not shape {tuple(d_sig96.shape)}")
+        ins, snd = self._coin_items("add_sig_shares_d", inst, sender, count, n)
+        if d_status is not None and (d_status.numel() != count or d_status.element_size() != 1):
+            raise ValueError(f"add_sig_shares_d: d_status must have one byte per share ({count})")
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        self._check(self.lib.hbx_add_sig_shares_d(
+            self.h, d_sig96.data_ptr() if count else None, ins.ctypes.data_as(u32p) if count else None,
+            snd.ctypes.data_as(u32p) if count else None, count, int(n),
+            None if d_status is None or not count else d_status.data_ptr(), self._stream(stream)))
+
+    def combine_signatures_insts(self, master_pk48: bytes, t: int, insts, use=None, sig=None, status=None, ok=None,
+                                 parity=None):
+        """hbx_combine_signatures_insts: the listed instances only -> (sig uint8[count, 96], status
+        int32[count], master_ok uint8[count], parity uint8[count]); `use` uint8[count, n] or None.  The
+        four outputs, if given, are the caller's arrays: only the listed instances' entries of them
+        are written."""
+        insts = self._coin_insts("combine_signatures_insts", insts)
+        count = getattr(self, "_coin_count", 0)
+        if insts.size and int(insts.max()) >= count:
+            raise ValueError(f"combine_signatures_insts: instance {int(insts.max())} of {count} prepared nonces")
+        if use is not None:
+            use = np.asarray(use)
+            if use.dtype != np.uint8 or use.ndim != 2 or use.shape[0] != count:
+                raise ValueError(f"combine_signatures_insts: use must be uint8[{count}, n], not {use.dtype}{use.shape}")
+            use = np.ascontiguousarray(use)
+        sig = np.zeros((count, 96), dtype=np.uint8) if sig is None else sig
+        status = np.zeros(count, dtype=np.int32) if status is None else status
+        ok = np.zeros(count, dtype=np.uint8) if ok is None else ok
+        parity = np.zeros(count, dtype=np.uint8) if parity is None else parity
+        for name, a, dt, shape in (("sig", sig, np.uint8, (count, 96)), ("status", status, np.int32, (count,)),
+                                   ("ok", ok, np.uint8, (count,)), ("parity", parity, np.uint8, (count,))):
+            if not isinstance(a, np.ndarray) or a.dtype != dt or a.shape != shape or not a.flags.c_contiguous:
+                raise ValueError(f"combine_signatures_insts: {name} must be contiguous {np.dtype(dt).name}{list(shape)}")
+        mpk = np.frombuffer(bytes(master_pk48), dtype=np.uint8).copy()
+        if insts.size:
+            self._check(self.lib.hbx_combine_signatures_insts(
+                self.h, _u8(mpk), t, insts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), insts.size,
+                None if use is None else _u8(use), _u8(sig), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                _u8(ok), _u8(parity)))
+        return sig, status, ok, parity
+
+    def combine_signatures_insts_d(self, master_pk48: bytes, t: int, insts, d_use=None, d_sig=None, d_status=None,
+                                   d_ok=None, d_parity=None, stream=None):
+        """hbx_combine_signatures_insts_d: insts a host list of coin instances; d_use / outputs as for
+        combine_signatures_d (only the listed instances' entries are written)."""
+        insts = self._coin_insts("combine_signatures_insts_d", insts)
+        import torch
+
+        for name, x, dt in (("d_use", d_use, torch.uint8), ("d_sig", d_sig, torch.uint8), ("d_status", d_status, torch.int32),
+                            ("d_ok", d_ok, torch.uint8), ("d_parity", d_parity, torch.uint8)):
+            if x is not None and (x.dtype != dt or not x.is_contiguous()):
+                raise ValueError(f"combine_signatures_insts_d: {name} must be a contiguous {dt} tensor")
+        mpk = np.frombuffer(bytes(master_pk48), dtype=np.uint8).copy()
+        opt = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        self._check(self.lib.hbx_combine_signatures_insts_d(
+            self.h, _u8(mpk), t, insts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if insts.size else None, insts.size,
+            opt(d_use), opt(d_sig), opt(d_status), opt(d_ok), opt(d_parity), self._stream(stream)))
+
+    def coin_tiles_used(self) -> int:
+        """Check blocks of the last signature-share check launch (hbx_get_coin_tiles_used)."""
+        return int(self.lib.hbx_get_coin_tiles_used(self.h))
 
     def verify_sigs(self, pk48: np.ndarray, msgs, sig96: np.ndarray) -> np.ndarray:
         """PublicKey::verify(sig_i, msg_i) for independent items (DHB votes, key-generation

@@ -450,6 +450,67 @@ int hbx_combine_signatures_d(hbx_ctx* ctx, const uint8_t* master_pk48, uint32_t 
 int hbx_get_coin_lanes_used(const hbx_ctx* ctx);
 
 /* ---------------------------------------------------------------------------------------------
+ * Common Coin, incremental: the signature shares that arrive while a node runs its coin instances,
+ * verified on arrival and merged into the round's [I][n] matrix, and the combine of the instances
+ * that crossed the threshold.  Where hbx_verify_sig_shares[_d] and hbx_combine_signatures[_d]
+ * decide a finished round, these serve a node that is running one.
+ *
+ * hbx_add_sig_shares[_d] -- CommonCoin::handle_share (src/common_coin.rs:149-161).  Item k is the
+ * 96 bytes sig96[k] for position (inst[k] < I prepared nonces, sender[k] = node index); the launch
+ * covers the tiles of the check kernels that the items touch, not I * n.  Lanes per check: the
+ * matrix call's rule over the touched one-lane tiles (2 when fewer than 1024, else 1;
+ * hbx_set_verify_lanes 1 / 2 override); hbx_get_coin_lanes_used, hbx_debug_force_fallback and
+ * hbx_get_fallback_lanes mean for an add what they mean for a matrix verification.
+ *
+ * The matrix: after a hbx_verify_sig_shares[_d] since the latest hbx_prepare_nonces the add
+ * continues from that call's matrix (n must be its n).  Otherwise the first add establishes a matrix
+ * of width n with every entry HBX_SHARE_ABSENT, without any pairing work; count == 0 is allowed
+ * (pointers may then be NULL) and only does that.  hbx_prepare_nonces, hbx_set_digest and
+ * hbx_set_pk_shares void the matrix.
+ *
+ * status[k] for sender[k] < n is the HBX_SHARE_* byte hbx_verify_sig_shares_d writes for the same
+ * bytes at (inst[k], sender[k]): HBX_SHARE_UNKNOWN_SENDER for n_keys <= sender < n, and
+ * HBX_SHARE_UNDECODABLE for a point on the curve but outside G2.  sender[k] >= n touches no
+ * position: HBX_SHARE_UNDECODABLE when the bytes do not decode to a point of G2 (the reference never
+ * sees a message serde rejects), else HBX_SHARE_UNKNOWN_SENDER (Err(UnknownSender), :158).
+ * Merge: an entry that is HBX_SHARE_VALID keeps its point and status when the item is not VALID
+ * (the fault is returned before `insert`, :151-155); in every other case the entry takes the item's
+ * status, and its point where it decoded (`insert`, :156).  No other entry changes, so delivering
+ * every share of a round once, in any partition into calls, leaves hbx_get_sig_share_status and
+ * every combine as one matrix call does.
+ *
+ * HBX_E_INVALID_ARG before anything is launched, nothing changed: inst[k] >= I; the same
+ * (inst, sender) twice in one call (the second message of a pair goes into a later call); n
+ * different from the matrix's; n == 0.  HBX_E_NO_KEYS / HBX_E_NO_CIPHERTEXTS as for the matrix call.
+ * The host index arrays are consumed before the call returns.  The _d form is stream-ordered and
+ * does not synchronise (d_status may be NULL); the host form blocks.
+ *
+ * hbx_combine_signatures_insts[_d] -- try_output and combine_and_verify_sig (src/common_coin.rs:163-207)
+ * for the listed instances only: what hbx_combine_signatures_d does (the first t VALID entries in
+ * index order at call time, restricted by d_use [I][n] when given), writing only the listed
+ * instances' entries of the four outputs ([I][96], [I] int32, [I], [I] bytes; each may be NULL): no
+ * other byte changes.  insts (HOST, consumed before the call returns): an instance >= I or one
+ * listed twice is HBX_E_INVALID_ARG; ninsts == 0 returns HBX_OK and does nothing.  The host form
+ * takes use as bytes [I][n] (or NULL) and writes master_ok / parity as bytes [I], not bits.
+ * ------------------------------------------------------------------------------------------- */
+int hbx_add_sig_shares_d(hbx_ctx* ctx, const uint8_t* d_sig96 /* [count][96] */,
+                         const uint32_t* inst /* HOST [count] */, const uint32_t* sender /* HOST [count] */,
+                         uint32_t count, uint32_t n, uint8_t* d_status /* [count], may be NULL */, void* stream);
+int hbx_add_sig_shares(hbx_ctx* ctx, const uint8_t* sig96, const uint32_t* inst, const uint32_t* sender,
+                       uint32_t count, uint32_t n, uint8_t* status);
+int hbx_combine_signatures_insts_d(hbx_ctx* ctx, const uint8_t* master_pk48, uint32_t t,
+                                   const uint32_t* insts /* HOST [ninsts] */, uint32_t ninsts,
+                                   const uint8_t* d_use /* [I][n] or NULL */, uint8_t* d_sig96 /* [I][96] */,
+                                   int32_t* d_status /* [I] */, uint8_t* d_master_ok, uint8_t* d_parity, void* stream);
+int hbx_combine_signatures_insts(hbx_ctx* ctx, const uint8_t* master_pk48, uint32_t t, const uint32_t* insts,
+                                 uint32_t ninsts, const uint8_t* use /* bytes [I][n] or NULL */, uint8_t* sig96,
+                                 int32_t* status, uint8_t* master_ok /* bytes [I] */, uint8_t* parity /* bytes [I] */);
+/* Check blocks (64-thread tiles) of the last signature-share check launch: grid.x * grid.y for a
+ * matrix verification, the tile-list length for an add (0 when no item had sender < n); 0 before
+ * any.  Diagnostics: no reference counterpart. */
+uint32_t hbx_get_coin_tiles_used(const hbx_ctx* ctx);
+
+/* ---------------------------------------------------------------------------------------------
  * Dynamic HoneyBadger / key-generation signatures: threshold_crypto
  * PublicKey::verify(sig, msg) = e(pk, hash_g2(msg)) == e(g1, sig) for `count` independent items,
  * each with its own key, message and signature -- the signed votes of
