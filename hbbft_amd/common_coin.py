@@ -37,7 +37,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .hbx import SHARE_INVALID, SHARE_UNDECODABLE, SHARE_UNKNOWN_SENDER, SHARE_VALID
+from .hbx import SHARE_INVALID, SHARE_UNDECODABLE, SHARE_UNKNOWN_SENDER, SHARE_VALID, layers
 
 UNVERIFIED_SIGNATURE_SHARE_SENDER = "UnverifiedSignatureShareSender"
 UNKNOWN_SENDER = "UnknownSender"
@@ -112,6 +112,87 @@ class _Inst:
         self.terminated = False
         self.received: Dict[int, int] = {}  # sender -> message id (BTreeMap<N, SignatureShare>)
 
+    def copy(self) -> "_Inst":
+        c = _Inst()
+        c.had_input, c.terminated, c.received = self.had_input, self.terminated, dict(self.received)
+        return c
+
+
+def _replay(events, msgs, msg_of_event, status, insts, known, held_key, n: int, f: int, me: Optional[int]):
+    """The reference's control flow over ``events`` with the engine's status of every share message
+    (``status[m]``, ``m = msg_of_event[k]``) -> (CoinResult, pending).  ``insts``: the state every
+    instance starts from, advanced in place.  ``known``: (inst, key of the held set) -> (error,
+    parity) of the combinations run so far, ``held_key(received)`` the key of a held set in it; an
+    instance whose set is not in ``known`` goes into ``pending`` (inst -> key) and is taken to
+    terminate, to be combined after this pass.
+
+    Two cases arise in ``CoinSession`` alone: an event with no message (its instance terminated
+    before the flush) and the status SHARE_UNKNOWN_SENDER (our own share when ``me`` is no
+    validator).  ``CoinReplay`` gives every share event a message and its engine never returns that
+    status."""
+    res = CoinResult()
+    pending: dict = {}
+
+    def try_output(inst, who):
+        b = insts[inst]
+        if not (b.had_input and len(b.received) > f):
+            return
+        senders, key = tuple(sorted(b.received)), held_key(b.received)
+        r = known.get((inst, key))
+        if r is None:
+            pending[inst] = key  # combined after this pass; taken to succeed meanwhile
+            b.terminated = True
+            return
+        err, par = r
+        res.combines.append((inst, senders, err is None))
+        if err is not None:
+            res.errors.append((who, err))
+            return
+        b.terminated = True
+        res.outputs.append((inst, par))
+
+    def handle_share(inst, sender, m, who):
+        st = status[m]
+        if st == SHARE_UNKNOWN_SENDER:
+            res.errors.append((who, UNKNOWN_SENDER))
+            return
+        if st != SHARE_VALID:
+            if st == SHARE_INVALID:
+                res.faults.append((sender, UNVERIFIED_SIGNATURE_SHARE_SENDER))
+            return
+        insts[inst].received[sender] = m
+        try_output(inst, who)
+
+    for k, ev in enumerate(events):
+        if ev[0] == "input":
+            inst = ev[1]
+            b = insts[inst]
+            if b.had_input:
+                continue
+            b.had_input = True
+            if me is None:
+                try_output(inst, None)
+                continue
+            m = msg_of_event[k]
+            # get_coin (common_coin.rs:142-146): an error from our own share's handle_share
+            # drops the step with the outgoing message (the `?`); the error is our input's
+            n_err = len(res.errors)
+            handle_share(inst, me, m, None)
+            if len(res.errors) == n_err:
+                res.sent.append((inst, msgs[m][2]))
+        else:
+            _, sender, inst, _ = ev
+            m = msg_of_event.get(k)
+            if m is None or status[m] == SHARE_UNDECODABLE:
+                continue  # terminated before the flush, or rejected by serde before CommonCoin
+            if insts[inst].terminated:
+                continue  # handle_message after termination (:105-110)
+            if not 0 <= sender < n:
+                res.errors.append((sender, UNKNOWN_SENDER))
+                continue
+            handle_share(inst, sender, m, sender)
+    return res, pending
+
 
 class CoinReplay:
     """Every CommonCoin instance of a round at node ``me`` (None: an observer, not a validator)."""
@@ -155,7 +236,10 @@ class CoinReplay:
         known: Dict[Tuple[int, Tuple[Tuple[int, int], ...]], Tuple[Optional[str], bool]] = {}  # -> (error, parity)
         combines_run = 0
         while True:
-            res, pending = self._replay(events, msgs, msg_of_event, status, known, count)
+            # from a fresh round each pass; a held set is keyed by its (sender, message id) pairs:
+            # a sender's repeated message is another share
+            res, pending = _replay(events, msgs, msg_of_event, status, [_Inst() for _ in range(count)], known,
+                                   lambda received: tuple(sorted(received.items())), n, self.f, self.me)
             if not pending:
                 break
             combines_run += 1
@@ -188,24 +272,16 @@ class CoinReplay:
             st = self._verify_layer(batch, msgs, count)
             for key, m in batch.items():
                 status[m] = SHARE_UNDECODABLE if st[key] == SHARE_UNDECODABLE else SHARE_INVALID
-        layers: List[Dict[Tuple[int, int], int]] = []
-        seen: Dict[Tuple[int, int], int] = {}
         layer_of = [-1] * len(msgs)
-        for m, (inst, sender, _) in enumerate(msgs):
-            if not 0 <= sender < n:
-                continue
-            key = (inst, sender)
-            L = seen.get(key, 0)
-            seen[key] = L + 1
-            if L == len(layers):
-                layers.append({})
-            layers[L][key] = m
-            layer_of[m] = L
-        for layer in layers:
+        real = [m for m, (_, sender, _) in enumerate(msgs) if 0 <= sender < n]
+        self._last_layer = -1
+        for L, idx in enumerate(layers([msgs[m][:2] for m in real])):
+            layer = {msgs[real[i]][:2]: real[i] for i in idx}
             st = self._verify_layer(layer, msgs, count)
             for key, m in layer.items():
                 status[m] = st[key]
-        self._last_layer = len(layers) - 1
+                layer_of[m] = L
+            self._last_layer = L
         return status, layer_of
 
     def _verify_layer(self, layer, msgs, count):
@@ -215,70 +291,6 @@ class CoinReplay:
             sigs[key] = np.frombuffer(msgs[m][2], dtype=np.uint8)
             present[key] = 1
         return self.engine.verify(sigs, present)
-
-    def _replay(self, events, msgs, msg_of_event, status, known, count):
-        res = CoinResult()
-        insts = [_Inst() for _ in range(count)]
-        pending: Dict[int, Tuple[Tuple[int, int], ...]] = {}  # inst -> held (sender, msg id) set
-
-        def try_output(inst, who):
-            b = insts[inst]
-            if not (b.had_input and len(b.received) > self.f):
-                return
-            held = tuple(sorted(b.received.items()))
-            senders = tuple(s for s, _ in held)
-            r = known.get((inst, held))
-            if r is None:
-                pending[inst] = held  # combined after this pass; taken to succeed meanwhile
-                b.terminated = True
-                return
-            err, par = r
-            res.combines.append((inst, senders, err is None))
-            if err is not None:
-                res.errors.append((who, err))
-                return
-            b.terminated = True
-            res.outputs.append((inst, par))
-
-        def handle_share(inst, sender, m, who):
-            b = insts[inst]
-            st = status[m]
-            if st != SHARE_VALID:
-                if st == SHARE_INVALID:
-                    res.faults.append((sender, UNVERIFIED_SIGNATURE_SHARE_SENDER))
-                return
-            b.received[sender] = m
-            try_output(inst, who)
-
-        for k, ev in enumerate(events):
-            if ev[0] == "input":
-                inst = ev[1]
-                b = insts[inst]
-                if b.had_input:
-                    continue
-                b.had_input = True
-                if self.me is None:
-                    try_output(inst, None)
-                    continue
-                m = msg_of_event[k]
-                # get_coin (common_coin.rs:142-146): an error from our own share's handle_share
-                # drops the step with the outgoing message (the `?`); the error is our input's
-                n_err = len(res.errors)
-                handle_share(inst, self.me, m, None)
-                if len(res.errors) == n_err:
-                    res.sent.append((inst, msgs[m][2]))
-            else:
-                _, sender, inst, _ = ev
-                b = insts[inst]
-                if status[msg_of_event[k]] == SHARE_UNDECODABLE:
-                    continue  # rejected by serde before CommonCoin
-                if b.terminated:
-                    continue  # handle_message after termination (:105-110)
-                if not 0 <= sender < self.n:
-                    res.errors.append((sender, UNKNOWN_SENDER))
-                    continue
-                handle_share(inst, sender, msg_of_event[k], sender)
-        return res, pending
 
     def _combine(self, pending, msgs, layer_of, known, count):
         """One engine combine over the pending sets.  When every held share is in the last
@@ -422,7 +434,11 @@ class CoinSession:
                 res_status[k] = int(status[m])
         combines_run = 0
         while True:
-            res, pending, insts = self._replay(events, msgs, msg_of_event, status)
+            # from the state the last flush left; a held set is keyed by its senders: the matrix
+            # holds one share per sender
+            insts = [b.copy() for b in self._insts]
+            res, pending = _replay(events, msgs, msg_of_event, status, insts, self._known,
+                                   lambda received: tuple(sorted(received)), n, self.f, self.me)
             if not pending:
                 break
             combines_run += 1
@@ -437,89 +453,12 @@ class CoinSession:
         """One engine add per layer (layer L = the L-th message of each (inst, sender) pair in this
         flush), in order, so the matrix ends as message-by-message delivery leaves it."""
         status = np.full(len(msgs), SHARE_UNDECODABLE, dtype=np.int32)
-        layers: List[List[int]] = []
-        seen: Dict[Tuple[int, int], int] = {}
-        for m, (inst, sender, _) in enumerate(msgs):
-            L = seen.get((inst, sender), 0)
-            seen[(inst, sender)] = L + 1
-            if L == len(layers):
-                layers.append([])
-            layers[L].append(m)
-        for layer in layers:
+        for layer in layers([msg[:2] for msg in msgs]):
             sig = np.frombuffer(b"".join(msgs[m][2] for m in layer), dtype=np.uint8).reshape(len(layer), 96)
             st = self.engine.add(sig, [msgs[m][0] for m in layer], [msgs[m][1] for m in layer], self.n)
             self.engine_adds += 1
             status[layer] = st
         return status
-
-    def _replay(self, events, msgs, msg_of_event, status):
-        res = CoinResult()
-        insts = []
-        for b in self._insts:
-            c = _Inst()
-            c.had_input, c.terminated, c.received = b.had_input, b.terminated, dict(b.received)
-            insts.append(c)
-        pending: Dict[int, Tuple[int, ...]] = {}  # inst -> the senders held at the trigger
-
-        def try_output(inst, who):
-            b = insts[inst]
-            if not (b.had_input and len(b.received) > self.f):
-                return
-            senders = tuple(sorted(b.received))
-            r = self._known.get((inst, senders))
-            if r is None:
-                pending[inst] = senders  # combined after this pass; taken to succeed meanwhile
-                b.terminated = True
-                return
-            err, par = r
-            res.combines.append((inst, senders, err is None))
-            if err is not None:
-                res.errors.append((who, err))
-                return
-            b.terminated = True
-            res.outputs.append((inst, par))
-
-        def handle_share(inst, sender, m, who):
-            st = status[m]
-            if st == SHARE_UNKNOWN_SENDER:
-                res.errors.append((who, UNKNOWN_SENDER))
-                return
-            if st != SHARE_VALID:
-                if st == SHARE_INVALID:
-                    res.faults.append((sender, UNVERIFIED_SIGNATURE_SHARE_SENDER))
-                return
-            insts[inst].received[sender] = m
-            try_output(inst, who)
-
-        for k, ev in enumerate(events):
-            if ev[0] == "input":
-                inst = ev[1]
-                b = insts[inst]
-                if b.had_input:
-                    continue
-                b.had_input = True
-                if self.me is None:
-                    try_output(inst, None)
-                    continue
-                m = msg_of_event[k]
-                # get_coin (common_coin.rs:142-146): an error from our own share's handle_share
-                # drops the step with the outgoing message (the `?`); the error is our input's
-                n_err = len(res.errors)
-                handle_share(inst, self.me, m, None)
-                if len(res.errors) == n_err:
-                    res.sent.append((inst, msgs[m][2]))
-            else:
-                _, sender, inst, _ = ev
-                m = msg_of_event.get(k)
-                if m is None or status[m] == SHARE_UNDECODABLE:
-                    continue  # terminated before the flush, or rejected by serde before CommonCoin
-                if insts[inst].terminated:
-                    continue  # handle_message after termination (:105-110)
-                if not 0 <= sender < self.n:
-                    res.errors.append((sender, UNKNOWN_SENDER))
-                    continue
-                handle_share(inst, sender, m, sender)
-        return res, pending, insts
 
     def _combine(self, pending):
         """One engine combine over the instances that triggered, each over the shares it held then."""

@@ -134,6 +134,30 @@ struct timing_state {
   }
 };
 
+// The state of an incremental add, one per share kind (hbx_add_dec_shares_d: rows = proposers, g1a;
+// hbx_add_sig_shares_d: rows = instances, g2a).  The candidates of an add are decoded and checked
+// apart from the held matrix, in the same [rows][n] layout (only the add's tiles are ever written or
+// read): their points, decode statuses and verdicts.  `mask` holds the add's positions as the tile
+// launch's present mask, all 0 between calls; mask_m = the bytes of it known to be 0.  item_st: the
+// statuses of the items that touch no position (the coin's decode alone writes them).  in / out:
+// the host form's staging of the items' bytes and of their statuses.
+struct add_state {
+  dbuf pts, pt_st, verdict, mask, item_st, in, out;
+  size_t mask_m = 0;
+  bool ensure(size_t m, size_t pt_bytes) {
+    return pts.ensure(m * pt_bytes) && pt_st.ensure(m * 4) && verdict.ensure(m) && mask.ensure(m);
+  }
+  // Before the add's launches: zeroes the mask if it is a new buffer or an interrupted call left
+  // it marked; from here to end() it counts as marked.
+  hipError_t begin(size_t m, hipStream_t s) {
+    const hipError_t e = mask_m < m ? hipMemsetAsync(mask.p, 0, mask.cap, s) : hipSuccess;
+    mask_m = 0;
+    return e;
+  }
+  // After the merge is enqueued: it clears every byte the decode set.
+  void end() { mask_m = mask.cap; }
+};
+
 }  // namespace
 
 struct hbx_ctx {
@@ -177,12 +201,10 @@ struct hbx_ctx {
   dbuf S, S_status, fallback, valid, shares_own, present_own, gslot;
   dbuf fe1slot;  // one-lane checks: the final exponentiation's global slots F, T, G (fe1d.hpp)
   uint32_t verify_tiles = 0;  // check blocks of the last share-check launch (hbx_get_verify_tiles_used)
-  // hbx_add_dec_shares_d: the candidates of an add, decoded and checked apart from the epoch's
-  // matrix (same p x n layout; only the add's tiles are ever written or read), the positions of the
-  // add as the tile launch's present mask (all 0 between calls; add_mask_m = the bytes known to be
-  // 0), and the host form's staging
-  dbuf add_S, add_status, add_valid, add_mask, add_zero, add_shares, add_dst;
-  size_t add_mask_m = 0;
+  // hbx_add_dec_shares_d: the add's state, and the all-absent shares and present mask that
+  // establish the epoch's matrix
+  add_state dec_add;
+  dbuf add_zero;
   uint32_t force_fallback = 0;  // hbx_debug_force_fallback (tests only)
   uint32_t force_degen = 0;  // hbx_debug_force_degenerate (tests only)
   // the combine's window tables (g1d.hpp; built by k_prepare_lines in the fused epoch call only):
@@ -239,15 +261,11 @@ struct hbx_ctx {
   dbuf coin_use;      // hbx_combine_signatures_d: the verified shares masked by the caller's subset
   // hbx_add_sig_shares_d: coin_live = the [coin_I][coin_n] matrix belongs to the prepared nonces and
   // the current keys (read by the add alone: a matrix verification or an add sets it;
-  // hbx_prepare_nonces, hbx_set_digest and hbx_set_pk_shares clear it).  The candidates of an add are
-  // decoded and checked apart from the round's matrix (same layout; only the add's tiles are ever
-  // written or read), coin_add_mask holds the add's positions as the tile launch's present mask (all
-  // 0 between calls; coin_add_mask_m = the bytes known to be 0), coin_add_ist the statuses of the
-  // items that touch no position; then the host forms' staging.
+  // hbx_prepare_nonces, hbx_set_digest and hbx_set_pk_shares clear it); sig_add = the add's state.
   bool coin_live = false;
   uint32_t coin_tiles = 0;  // check blocks of the last signature-share launch (hbx_get_coin_tiles_used)
-  dbuf coin_add_sig, coin_add_st, coin_add_valid, coin_add_mask, coin_add_ist, coin_add_sig96, coin_add_dst, coin_use_in;
-  size_t coin_add_mask_m = 0;
+  add_state sig_add;
+  dbuf coin_use_in;  // hbx_combine_signatures_insts: the host form's staging of `use`
   // SyncKeyGen commitment checks (hbx_bivar_rows / hbx_bivar_check_acks)
   dbuf bv_commit48, bv_C, bv_cst, bv_rows, bv_rows48, bv_pst, bv_ackp, bv_acky, bv_vals, bv_out;
   // SyncKeyGen SecretKey::decrypt (hbx_sk_decrypt): the key's limbs, plaintexts, HBX_CT_* per ciphertext
@@ -1405,6 +1423,76 @@ static int staging_upload(hbx_ctx* c, size_t bytes, hipStream_t s) {
   return HBX_OK;
 }
 
+// Every listed index is below `bound` and listed once (before anything is launched); `name` is the
+// caller's array, `noun` what an entry of it names.
+static int list_check(hbx_ctx* c, const char* fn, const char* name, const uint32_t* idx, uint32_t count, uint32_t bound,
+                      const char* noun) {
+  std::vector<uint8_t> seen(bound, 0);
+  for (uint32_t k = 0; k < count; k++) {
+    if (idx[k] >= bound || seen[idx[k]])
+      return fail(c, HBX_E_INVALID_ARG, "%s: %s[%u] = %u is %s%s", fn, name, k, idx[k],
+                  idx[k] >= bound ? "not a prepared " : "listed twice", idx[k] >= bound ? noun : "");
+    seen[idx[k]] = 1;
+  }
+  return HBX_OK;
+}
+
+// ---- the incremental adds' common host steps (hbx_add_dec_shares_d, hbx_add_sig_shares_d) -------
+// What addplan's build() refused, as entry point `fn`'s error; `row` = what an item's first index
+// names, `row_bound` = the text for one that is not below `rows` (one %u).
+static int add_plan_rejected(hbx_ctx* c, int plan_rc, const char* fn, const char* row, const char* row_bound,
+                             uint32_t rows, uint32_t me) {
+  char text[96];
+  switch (plan_rc) {
+    case hbx_addplan::PLAN_BAD_PROPOSER:
+      snprintf(text, sizeof text, row_bound, rows);
+      return fail(c, HBX_E_INVALID_ARG, "%s: %s", fn, text);
+    case hbx_addplan::PLAN_DUPLICATE:
+      return fail(c, HBX_E_INVALID_ARG, "%s: the same (%s, sender) twice in one call", fn, row);
+    case hbx_addplan::PLAN_OWN_SENDER:
+      return fail(c, HBX_E_INVALID_ARG, "%s: sender %u is this node (own-share mode)", fn, me);
+    default:
+      return HBX_OK;
+  }
+}
+
+// An add's items as (row, sender) pairs and the tile list of the chosen shape, into the pinned
+// staging and up in one copy on `s`: the caller's arrays are consumed before the call returns.
+static int add_stage(hbx_ctx* c, const char* fn, const uint32_t* row, const uint32_t* sender, uint32_t count,
+                     const std::vector<hbx_addplan::tile>& tiles, hipStream_t s, const uint2** d_items,
+                     const uint2** d_tiles) {
+  const size_t items_bytes = (size_t)count * sizeof(uint2), tiles_bytes = tiles.size() * sizeof(uint2);
+  uint8_t* pin = staging_begin(c, items_bytes + tiles_bytes);
+  if (!pin) return fail(c, HBX_E_OUT_OF_MEMORY, "%s: out of memory (staging)", fn);
+  uint2* it = reinterpret_cast<uint2*>(pin);
+  for (uint32_t k = 0; k < count; k++) it[k] = make_uint2(row[k], sender[k]);
+  if (tiles_bytes) memcpy(pin + items_bytes, tiles.data(), tiles_bytes);
+  if (int rc = staging_upload(c, items_bytes + tiles_bytes, s)) return rc;
+  *d_items = c->rg_dev.as<uint2>();
+  *d_tiles = reinterpret_cast<const uint2*>(c->rg_dev.as<uint8_t>() + items_bytes);
+  return HBX_OK;
+}
+
+// The host form of an add, on the context's stream: the items' bytes (`width` each) up into the
+// add state's `in`, the _d form `add_d` with its statuses into `out`, those read back; synchronised
+// at return.
+static int add_host(hbx_ctx* c, const char* fn, add_state hbx_ctx::*state, size_t width,
+                    decltype(&hbx_add_dec_shares_d) add_d, const uint8_t* bytes, const uint32_t* row,
+                    const uint32_t* sender, uint32_t count, uint32_t n, uint8_t* status) {
+  if (!c || n == 0 || (count && (!bytes || !row || !sender))) return fail(c, HBX_E_INVALID_ARG, "%s: bad args", fn);
+  HBX_ENTER(c, c->stream);
+  add_state& a = c->*state;
+  if (!a.in.ensure((size_t)count * width) || !a.out.ensure(count))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "%s: out of device memory", fn);
+  if (count) HIPCHK(c, hipMemcpyAsync(a.in.p, bytes, (size_t)count * width, hipMemcpyHostToDevice, c->stream));
+  if (int rc = add_d(c, a.in.as<uint8_t>(), row, sender, count, n, a.out.as<uint8_t>(), c->stream)) return rc;
+  std::vector<uint8_t> st(count);
+  if (count) HIPCHK(c, hipMemcpyAsync(st.data(), a.out.p, count, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (status && count) memcpy(status, st.data(), count);
+  return HBX_OK;
+}
+
 // The descriptor rules of include/hbx.h; max_len = the longest shard.
 static int rg_check(hbx_ctx* c, const char* fn, uint64_t buf_bytes, const uint64_t* off, const uint32_t* len,
                     const uint32_t* pitch, uint32_t inst, uint32_t n, uint32_t* max_len) {
@@ -2438,14 +2526,10 @@ int hbx_add_sig_shares_d(hbx_ctx* c, const uint8_t* d_sig96, const uint32_t* ins
   if (c->coin_live && n != c->coin_n)
     return fail(c, HBX_E_INVALID_ARG, "hbx_add_sig_shares_d: n=%u but the round's matrix has n=%u", n, c->coin_n);
   hbx_addplan::plan pl;
-  switch (hbx_addplan::build(inst, sender, count, n, I, UINT32_MAX, pl)) {
-    case hbx_addplan::PLAN_BAD_PROPOSER:
-      return fail(c, HBX_E_INVALID_ARG, "hbx_add_sig_shares_d: an instance index >= %u prepared nonces", I);
-    case hbx_addplan::PLAN_DUPLICATE:
-      return fail(c, HBX_E_INVALID_ARG, "hbx_add_sig_shares_d: the same (instance, sender) twice in one call");
-    default:
-      break;
-  }
+  if (int rc = add_plan_rejected(c, hbx_addplan::build(inst, sender, count, n, I, UINT32_MAX, pl), "hbx_add_sig_shares_d",
+                                 "instance", "an instance index >= %u prepared nonces", I, UINT32_MAX))
+    return rc;
+  // one stream for the whole call: establishing the matrix is two memsets on it
   HBX_ENTER(c, stream);
   const size_t m = (size_t)n * I;
   if (!c->coin_sig.ensure(m * sizeof(g2a)) || !c->coin_sig_st.ensure(m * 4) || !c->coin_valid.ensure(m))
@@ -2459,90 +2543,52 @@ int hbx_add_sig_shares_d(hbx_ctx* c, const uint8_t* d_sig96, const uint32_t* ins
     c->coin_live = true;
   }
   if (count == 0) return HBX_OK;
-  if (!c->coin_add_sig.ensure(m * sizeof(g2a)) || !c->coin_add_st.ensure(m * 4) || !c->coin_add_valid.ensure(m) ||
-      !c->coin_add_mask.ensure(m) || !c->coin_add_ist.ensure(count))
+  add_state& a = c->sig_add;
+  if (!a.ensure(m, sizeof(g2a)) || !a.item_st.ensure(count))
     return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_add_sig_shares_d: out of device memory");
-  if (c->coin_add_mask_m < m) {  // a new buffer, or one an interrupted call left marked
-    HIPCHK(c, hipMemsetAsync(c->coin_add_mask.p, 0, c->coin_add_mask.cap, s));
-  }
-  c->coin_add_mask_m = 0;
+  HIPCHK(c, a.begin(m, s));
   // lanes per check from what is live: the matrix call's rule over the touched one-lane tiles
   const int lanes = c->verify_lanes == 1 || c->verify_lanes == 2 ? c->verify_lanes
                     : pl.tiles[0].size() < FILL_WAVES ? 2 : 1;
   const std::vector<hbx_addplan::tile>& tiles = pl.tiles[hbx_addplan::shape_of_lanes(lanes)];
-  // the items and the tile list, consumed before the call returns (pinned staging, one upload)
-  const size_t items_bytes = (size_t)count * sizeof(uint2), tiles_bytes = tiles.size() * sizeof(uint2);
-  uint8_t* pin = staging_begin(c, items_bytes + tiles_bytes);
-  if (!pin) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_add_sig_shares_d: out of memory (staging)");
-  uint2* it = reinterpret_cast<uint2*>(pin);
-  for (uint32_t k = 0; k < count; k++) it[k] = make_uint2(inst[k], sender[k]);
-  if (tiles_bytes) memcpy(pin + items_bytes, tiles.data(), tiles_bytes);
-  if (int rc = staging_upload(c, items_bytes + tiles_bytes, s)) return rc;
-  const uint2* d_items = c->rg_dev.as<uint2>();
-  const uint2* d_tiles = reinterpret_cast<const uint2*>(c->rg_dev.as<uint8_t>() + items_bytes);
+  const uint2 *d_items, *d_tiles;
+  if (int rc = add_stage(c, "hbx_add_sig_shares_d", inst, sender, count, tiles, s, &d_items, &d_tiles)) return rc;
   {
     timed t_(c, HBX_K_DECODE_SIGS, s);
     hipLaunchKernelGGL(k_coin_add_decode, dim3((count + 63) / 64), dim3(64), 0, s, d_sig96, d_items, count, n,
-                       c->coin_add_sig.as<g2a>(), c->coin_add_st.as<int32_t>(), c->coin_add_mask.as<uint8_t>(),
-                       c->coin_add_ist.as<uint8_t>());
+                       a.pts.as<g2a>(), a.pt_st.as<int32_t>(), a.mask.as<uint8_t>(), a.item_st.as<uint8_t>());
   }
   HIPCHK(c, hipGetLastError());
   if (pl.live) {
     if (int rc = coin_prepare_lines(c, s)) return rc;
-    if (int rc = launch_sig_checks(c, s, lanes, dim3((unsigned)tiles.size(), 1), d_tiles, c->coin_add_sig.as<g2a>(),
-                                   c->coin_add_st.as<int32_t>(), c->coin_add_mask.as<uint8_t>(), n,
-                                   c->coin_add_valid.as<uint8_t>()))
+    if (int rc = launch_sig_checks(c, s, lanes, dim3((unsigned)tiles.size(), 1), d_tiles, a.pts.as<g2a>(),
+                                   a.pt_st.as<int32_t>(), a.mask.as<uint8_t>(), n, a.verdict.as<uint8_t>()))
       return rc;
   } else {
     c->coin_tiles = 0;
     c->fb_last = nullptr;
   }
-  hipLaunchKernelGGL(k_coin_add_merge, dim3((count + 255) / 256), dim3(256), 0, s, d_items, count, n,
-                     c->coin_add_sig.as<g2a>(), c->coin_add_st.as<int32_t>(), c->coin_add_valid.as<uint8_t>(),
-                     c->coin_add_mask.as<uint8_t>(), c->coin_add_ist.as<uint8_t>(), c->coin_sig.as<g2a>(),
-                     c->coin_sig_st.as<int32_t>(), c->coin_valid.as<uint8_t>(), d_status);
+  hipLaunchKernelGGL(k_coin_add_merge, dim3((count + 255) / 256), dim3(256), 0, s, d_items, count, n, a.pts.as<g2a>(),
+                     a.pt_st.as<int32_t>(), a.verdict.as<uint8_t>(), a.mask.as<uint8_t>(), a.item_st.as<uint8_t>(),
+                     c->coin_sig.as<g2a>(), c->coin_sig_st.as<int32_t>(), c->coin_valid.as<uint8_t>(), d_status);
   HIPCHK(c, hipGetLastError());
-  c->coin_add_mask_m = c->coin_add_mask.cap;
+  a.end();
   return HBX_OK;
 }
 
 int hbx_add_sig_shares(hbx_ctx* c, const uint8_t* sig96, const uint32_t* inst, const uint32_t* sender, uint32_t count,
                        uint32_t n, uint8_t* status) {
-  if (!c || n == 0 || (count && (!sig96 || !inst || !sender)))
-    return fail(c, HBX_E_INVALID_ARG, "hbx_add_sig_shares: bad args");
-  HBX_ENTER(c, c->stream);
-  if (!c->coin_add_sig96.ensure((size_t)count * 96) || !c->coin_add_dst.ensure(count))
-    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_add_sig_shares: out of device memory");
-  if (count) HIPCHK(c, hipMemcpyAsync(c->coin_add_sig96.p, sig96, (size_t)count * 96, hipMemcpyHostToDevice, c->stream));
-  int rc = hbx_add_sig_shares_d(c, c->coin_add_sig96.as<uint8_t>(), inst, sender, count, n, c->coin_add_dst.as<uint8_t>(),
-                                c->stream);
-  if (rc) return rc;
-  std::vector<uint8_t> st(count);
-  if (count) HIPCHK(c, hipMemcpyAsync(st.data(), c->coin_add_dst.p, count, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (status && count) memcpy(status, st.data(), count);
-  return HBX_OK;
+  return add_host(c, "hbx_add_sig_shares", &hbx_ctx::sig_add, 96, hbx_add_sig_shares_d, sig96, inst, sender, count, n,
+                  status);
 }
 
 uint32_t hbx_get_coin_tiles_used(const hbx_ctx* c) { return c ? c->coin_tiles : 0; }
-
-// The listed instances must be prepared ones, each once (before anything is launched).
-static int coin_insts_check(hbx_ctx* c, const char* fn, const uint32_t* insts, uint32_t ninsts) {
-  std::vector<uint8_t> seen(c->coin_I, 0);
-  for (uint32_t k = 0; k < ninsts; k++) {
-    if (insts[k] >= c->coin_I || seen[insts[k]])
-      return fail(c, HBX_E_INVALID_ARG, "%s: insts[%u] = %u is %s", fn, k, insts[k],
-                  insts[k] >= c->coin_I ? "not a prepared instance" : "listed twice");
-    seen[insts[k]] = 1;
-  }
-  return HBX_OK;
-}
 
 int hbx_combine_signatures_insts_d(hbx_ctx* c, const uint8_t* master_pk48, uint32_t t, const uint32_t* insts,
                                    uint32_t ninsts, const uint8_t* d_use, uint8_t* d_sig96, int32_t* d_status,
                                    uint8_t* d_master_ok, uint8_t* d_parity, void* stream) {
   if (!c || (!insts && ninsts)) return fail(c, HBX_E_INVALID_ARG, "hbx_combine_signatures_insts_d: bad args");
-  if (int rc = coin_insts_check(c, "hbx_combine_signatures_insts_d", insts, ninsts)) return rc;
+  if (int rc = list_check(c, "hbx_combine_signatures_insts_d", "insts", insts, ninsts, c->coin_I, "instance")) return rc;
   if (ninsts == 0) return HBX_OK;
   HBX_ENTER(c, stream);
   // the listed instances, consumed before the call returns (pinned staging, as an add's items)
@@ -2564,7 +2610,7 @@ int hbx_combine_signatures_insts_d(hbx_ctx* c, const uint8_t* master_pk48, uint3
 int hbx_combine_signatures_insts(hbx_ctx* c, const uint8_t* master_pk48, uint32_t t, const uint32_t* insts, uint32_t ninsts,
                                  const uint8_t* use, uint8_t* sig96, int32_t* status, uint8_t* master_ok, uint8_t* parity) {
   if (!c || (!insts && ninsts)) return fail(c, HBX_E_INVALID_ARG, "hbx_combine_signatures_insts: bad args");
-  if (int rc = coin_insts_check(c, "hbx_combine_signatures_insts", insts, ninsts)) return rc;
+  if (int rc = list_check(c, "hbx_combine_signatures_insts", "insts", insts, ninsts, c->coin_I, "instance")) return rc;
   if (ninsts == 0) return HBX_OK;
   HBX_ENTER(c, c->stream);
   const uint32_t I = c->coin_I;
@@ -2612,13 +2658,7 @@ static int combine_impl(hbx_ctx* c, uint32_t t, uint8_t* d_out_blob, int32_t* d_
     return fail(c, HBX_E_NO_CIPHERTEXTS, "no verified shares for the prepared ciphertexts");
   const uint32_t p = c->p_ct;
   if (cols) {
-    std::vector<uint8_t> seen(p, 0);
-    for (uint32_t k = 0; k < ncols; k++) {
-      if (cols[k] >= p || seen[cols[k]])
-        return fail(c, HBX_E_INVALID_ARG, "hbx_combine_decrypt_cols_d: cols[%u] = %u is %s", k, cols[k],
-                    cols[k] >= p ? "not a prepared proposer" : "listed twice");
-      seen[cols[k]] = 1;
-    }
+    if (int rc = list_check(c, "hbx_combine_decrypt_cols_d", "cols", cols, ncols, p, "proposer")) return rc;
     if (ncols == 0) return HBX_OK;
   }
   HBX_ENTER(c, stream);
@@ -2783,16 +2823,11 @@ int hbx_add_dec_shares_d(hbx_ctx* c, const uint8_t* d_shares48, const uint32_t* 
     return fail(c, HBX_E_INVALID_ARG, "hbx_add_dec_shares_d: n=%u but the epoch's matrix has n=%u", n, c->n_shares);
   const uint32_t me = (c->own_ready && c->own_me < n) ? c->own_me : UINT32_MAX;
   hbx_addplan::plan pl;
-  switch (hbx_addplan::build(proposer, sender, count, n, p, me, pl)) {
-    case hbx_addplan::PLAN_BAD_PROPOSER:
-      return fail(c, HBX_E_INVALID_ARG, "hbx_add_dec_shares_d: a proposer index >= p=%u", p);
-    case hbx_addplan::PLAN_DUPLICATE:
-      return fail(c, HBX_E_INVALID_ARG, "hbx_add_dec_shares_d: the same (proposer, sender) twice in one call");
-    case hbx_addplan::PLAN_OWN_SENDER:
-      return fail(c, HBX_E_INVALID_ARG, "hbx_add_dec_shares_d: sender %u is this node (own-share mode)", me);
-    default:
-      break;
-  }
+  if (int rc = add_plan_rejected(c, hbx_addplan::build(proposer, sender, count, n, p, me, pl), "hbx_add_dec_shares_d",
+                                 "proposer", "a proposer index >= p=%u", p, me))
+    return rc;
+  // the device only: establishing the matrix is an entry of its own on the caller's stream
+  // (verify_impl), so this call picks the stream before it and again after it
   HBX_DEVICE(c);
   const size_t m = (size_t)n * p;
   if (!established) {
@@ -2810,72 +2845,47 @@ int hbx_add_dec_shares_d(hbx_ctx* c, const uint8_t* d_shares48, const uint32_t* 
   if (count == 0) return HBX_OK;
   hipStream_t s = pick(c, stream);
   stream_scope ss_{c, s};
-  if (!c->add_S.ensure(m * sizeof(g1a)) || !c->add_status.ensure(m * 4) || !c->add_valid.ensure(m) ||
-      !c->add_mask.ensure(m))
-    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_add_dec_shares_d: out of device memory");
-  if (c->add_mask_m < m) {  // a new buffer, or one an interrupted call left marked
-    HIPCHK(c, hipMemsetAsync(c->add_mask.p, 0, c->add_mask.cap, s));
-  }
-  c->add_mask_m = 0;
+  add_state& a = c->dec_add;
+  if (!a.ensure(m, sizeof(g1a))) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_add_dec_shares_d: out of device memory");
+  HIPCHK(c, a.begin(m, s));
   // lanes per check from what is live: the matrix call's ladder over the touched-tile counts
   const int lanes = c->verify_lanes ? c->verify_lanes : hbx_addplan::lanes_of(pl);
   const std::vector<hbx_addplan::tile>& tiles = pl.tiles[hbx_addplan::shape_of_lanes(lanes)];
-  // the items and the tile list, consumed before the call returns (pinned staging, one upload)
-  const size_t items_bytes = (size_t)count * sizeof(uint2), tiles_bytes = tiles.size() * sizeof(uint2);
-  uint8_t* pin = staging_begin(c, items_bytes + tiles_bytes);
-  if (!pin) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_add_dec_shares_d: out of memory (staging)");
-  uint2* it = reinterpret_cast<uint2*>(pin);
-  for (uint32_t k = 0; k < count; k++) it[k] = make_uint2(proposer[k], sender[k]);
-  if (tiles_bytes) memcpy(pin + items_bytes, tiles.data(), tiles_bytes);
-  if (int rc = staging_upload(c, items_bytes + tiles_bytes, s)) return rc;
-  const uint2* d_items = c->rg_dev.as<uint2>();
-  const uint2* d_tiles = reinterpret_cast<const uint2*>(c->rg_dev.as<uint8_t>() + items_bytes);
+  const uint2 *d_items, *d_tiles;
+  if (int rc = add_stage(c, "hbx_add_dec_shares_d", proposer, sender, count, tiles, s, &d_items, &d_tiles)) return rc;
   c->tab_ready = false;  // S is about to hold other shares than the tables were made from
   const unsigned item_blocks = (count + 255) / 256;
   {
     timed t_(c, HBX_K_VERIFY_SHARES, s);
     c->verify_tiles = (uint32_t)tiles.size();
     if (pl.live) {
-      hipLaunchKernelGGL(k_add_decode, dim3(item_blocks), dim3(256), 0, s, d_shares48, d_items, count, n,
-                         c->add_S.as<g1a>(), c->add_status.as<int32_t>(), c->add_mask.as<uint8_t>());
+      hipLaunchKernelGGL(k_add_decode, dim3(item_blocks), dim3(256), 0, s, d_shares48, d_items, count, n, a.pts.as<g1a>(),
+                         a.pt_st.as<int32_t>(), a.mask.as<uint8_t>());
       HIPCHK(c, hipGetLastError());
       c->lanes_used = lanes;
       // the add's own items always run the per-share checks (ct_ok, not a batched call's gate); the
       // own lane and the ciphertexts were decided when the matrix was established
-      if (int rc = launch_share_checks(c, s, lanes, dim3((unsigned)tiles.size(), 1), d_tiles, c->add_S.as<g1a>(),
-                                       c->add_status.as<int32_t>(), c->add_mask.as<uint8_t>(),
-                                       c->add_valid.as<uint8_t>(), c->ct_ok.as<uint8_t>(), n, UINT32_MAX, nullptr))
+      if (int rc = launch_share_checks(c, s, lanes, dim3((unsigned)tiles.size(), 1), d_tiles, a.pts.as<g1a>(),
+                                       a.pt_st.as<int32_t>(), a.mask.as<uint8_t>(), a.verdict.as<uint8_t>(),
+                                       c->ct_ok.as<uint8_t>(), n, UINT32_MAX, nullptr))
         return rc;
       HIPCHK(c, hipGetLastError());
     } else {
       c->fb_last = nullptr;
     }
-    hipLaunchKernelGGL(k_add_merge, dim3(item_blocks), dim3(256), 0, s, d_items, count, n, c->add_S.as<g1a>(),
-                       c->add_status.as<int32_t>(), c->add_valid.as<uint8_t>(), c->add_mask.as<uint8_t>(),
-                       c->ct_valid.as<uint8_t>(), c->S.as<g1a>(), c->S_status.as<int32_t>(), c->valid.as<uint8_t>(),
-                       d_status);
+    hipLaunchKernelGGL(k_add_merge, dim3(item_blocks), dim3(256), 0, s, d_items, count, n, a.pts.as<g1a>(),
+                       a.pt_st.as<int32_t>(), a.verdict.as<uint8_t>(), a.mask.as<uint8_t>(), c->ct_valid.as<uint8_t>(),
+                       c->S.as<g1a>(), c->S_status.as<int32_t>(), c->valid.as<uint8_t>(), d_status);
   }
   HIPCHK(c, hipGetLastError());
-  c->add_mask_m = c->add_mask.cap;
+  a.end();
   return HBX_OK;
 }
 
 int hbx_add_dec_shares(hbx_ctx* c, const uint8_t* shares48, const uint32_t* proposer, const uint32_t* sender,
                        uint32_t count, uint32_t n, uint8_t* status) {
-  if (!c || n == 0 || (count && (!shares48 || !proposer || !sender)))
-    return fail(c, HBX_E_INVALID_ARG, "hbx_add_dec_shares: bad args");
-  HBX_ENTER(c, c->stream);
-  if (!c->add_shares.ensure((size_t)count * 48) || !c->add_dst.ensure(count))
-    return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_add_dec_shares: out of device memory");
-  if (count) HIPCHK(c, hipMemcpyAsync(c->add_shares.p, shares48, (size_t)count * 48, hipMemcpyHostToDevice, c->stream));
-  int rc = hbx_add_dec_shares_d(c, c->add_shares.as<uint8_t>(), proposer, sender, count, n, c->add_dst.as<uint8_t>(),
-                                c->stream);
-  if (rc) return rc;
-  std::vector<uint8_t> st(count);
-  if (count) HIPCHK(c, hipMemcpyAsync(st.data(), c->add_dst.p, count, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (status && count) memcpy(status, st.data(), count);
-  return HBX_OK;
+  return add_host(c, "hbx_add_dec_shares", &hbx_ctx::dec_add, 48, hbx_add_dec_shares_d, shares48, proposer, sender, count,
+                  n, status);
 }
 
 uint32_t hbx_get_verify_tiles_used(const hbx_ctx* c) { return c ? c->verify_tiles : 0; }

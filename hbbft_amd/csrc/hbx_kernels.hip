@@ -1830,6 +1830,26 @@ __global__ void __launch_bounds__(64) k_batch_compress(const g1a* __restrict__ p
 }
 #endif
 
+// The insert rule of the two incremental adds (k_add_merge with g1a, k_coin_add_merge with g2a; the
+// reference's lines are cited there): item k, at matrix position idx, has verdict v, which is also
+// its status byte (d_status[k]; d_status may be nullptr).  A VALID entry stays when the candidate
+// is not VALID; otherwise the entry takes the candidate's status, and its point where it decoded.
+// The candidate matrix is apart from the held one, so a kept entry was never displaced.  Clears
+// the item's mask byte.
+template <class PT>
+__device__ __forceinline__ void add_insert(uint32_t k, size_t idx, uint8_t v, const PT* __restrict__ pts_c,
+                                           const int32_t* __restrict__ status_c, uint8_t* __restrict__ mask,
+                                           PT* __restrict__ pts, int32_t* __restrict__ status,
+                                           uint8_t* __restrict__ valid, uint8_t* __restrict__ d_status) {
+  mask[idx] = 0;
+  if (d_status) d_status[k] = v;
+  if (valid[idx] == HBX_SHARE_VALID && v != HBX_SHARE_VALID) return;
+  const int32_t st = status_c[idx];
+  valid[idx] = v;
+  status[idx] = st;
+  if (st == HBX_PT_OK || st == HBX_PT_INFINITY) pts[idx] = pts_c[idx];
+}
+
 #if HBX_IN_TU(1)
 // pk_m[i] = [3(x^2-1)] pk_i (once per key set): the G1 side of the share checks against
 // H' = [3(x^2-1)] H (k_prepare_ct).
@@ -1904,10 +1924,8 @@ __global__ void __launch_bounds__(256) k_add_decode(const uint8_t* __restrict__ 
 }
 
 // hbx_add_dec_shares_d, merge: the candidate's verdict, gated by the ciphertext's as k_gate_by_ct
-// does, is the item's status.  A VALID entry stays when the candidate is not VALID (the reference
-// returns the fault before `insert`, honey_badger.rs:198-201); otherwise the entry takes the
-// candidate's status, and its point where it decoded (`insert` replaces, :205-210).  The candidate
-// matrix is apart from the epoch's, so a kept entry was never displaced.  Clears the item's mask byte.
+// does, is the item's status; then add_insert (the reference returns the fault before `insert`,
+// honey_badger.rs:198-201; `insert` replaces, :205-210).
 __global__ void __launch_bounds__(256) k_add_merge(const uint2* __restrict__ items, uint32_t count, uint32_t n,
                                                    const g1a* __restrict__ S_c, const int32_t* __restrict__ status_c,
                                                    const uint8_t* __restrict__ valid_c, uint8_t* __restrict__ mask,
@@ -1924,13 +1942,7 @@ __global__ void __launch_bounds__(256) k_add_merge(const uint2* __restrict__ ite
   const size_t idx = (size_t)it.x * n + it.y;
   uint8_t v = valid_c[idx];
   if (ct_valid[it.x] != HBX_CT_VALID && v <= HBX_SHARE_VALID) v = HBX_SHARE_SKIPPED_CT;
-  mask[idx] = 0;
-  if (d_status) d_status[k] = v;
-  if (valid[idx] == HBX_SHARE_VALID && v != HBX_SHARE_VALID) return;
-  const int32_t st = status_c[idx];
-  valid[idx] = v;
-  s_status[idx] = st;
-  if (st == HBX_PT_OK || st == HBX_PT_INFINITY) S[idx] = S_c[idx];
+  add_insert(k, idx, v, S_c, status_c, mask, S, s_status, valid, d_status);
 }
 
 // hbx_combine_decrypt_cols_d: the listed proposers' combine statuses into the caller's array
@@ -1985,11 +1997,8 @@ __global__ void __launch_bounds__(64) k_coin_add_decode(const uint8_t* __restric
   mask[idx] = 1;
 }
 
-// hbx_add_sig_shares_d, merge: the candidate's verdict is the item's status.  A VALID entry stays
-// when the candidate is not VALID (the reference returns the fault before `insert`,
-// common_coin.rs:151-155); otherwise the entry takes the candidate's status, and its point where it
-// decoded (`insert` replaces, :156).  The candidate matrix is apart from the round's, so a kept
-// entry was never displaced.  Clears the item's mask byte.
+// hbx_add_sig_shares_d, merge: the candidate's verdict is the item's status; then add_insert (the
+// reference returns the fault before `insert`, common_coin.rs:151-155; `insert` replaces, :156).
 __global__ void __launch_bounds__(256) k_coin_add_merge(const uint2* __restrict__ items, uint32_t count, uint32_t n,
                                                         const g2a* __restrict__ sig_c, const int32_t* __restrict__ status_c,
                                                         const uint8_t* __restrict__ valid_c, uint8_t* __restrict__ mask,
@@ -2004,14 +2013,7 @@ __global__ void __launch_bounds__(256) k_coin_add_merge(const uint2* __restrict_
     return;
   }
   const size_t idx = (size_t)it.x * n + it.y;
-  const uint8_t v = valid_c[idx];
-  mask[idx] = 0;
-  if (d_status) d_status[k] = v;
-  if (valid[idx] == HBX_SHARE_VALID && v != HBX_SHARE_VALID) return;
-  const int32_t st = status_c[idx];
-  valid[idx] = v;
-  sig_status[idx] = st;
-  if (st == HBX_PT_OK || st == HBX_PT_INFINITY) sig[idx] = sig_c[idx];
+  add_insert(k, idx, valid_c[idx], sig_c, status_c, mask, sig, sig_status, valid, d_status);
 }
 
 // hbx_combine_signatures_insts_d: the listed instances' results into the caller's arrays (each may

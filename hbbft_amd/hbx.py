@@ -360,6 +360,20 @@ def unpack_bits(bits: np.ndarray, n: int) -> np.ndarray:
     return np.unpackbits(np.asarray(bits, dtype=np.uint8), bitorder="little")[:n].astype(bool)
 
 
+def layers(keys) -> list:
+    """An add (and a matrix verification) takes each (row, sender) position once per call, so a run
+    of messages goes in as layers: layer L = the indices into ``keys``, in order, whose key occurs
+    there for the L-th time (L = 0, 1, ...) -> list of index lists."""
+    out, seen = [], {}
+    for i, key in enumerate(keys):
+        L = seen.get(key, 0)
+        seen[key] = L + 1
+        if L == len(out):
+            out.append([])
+        out[L].append(i)
+    return out
+
+
 class Context:
     """One hbx context bound to a HIP device (``hbx_ctx_create``)."""
 
@@ -541,54 +555,91 @@ class Context:
             res.append(out[int(off[j]):int(off[j + 1])].tobytes() if st[j] == HBX_OK else None)
         return res, st
 
+    # -- the incremental adds (hbx_add_dec_shares[_d], hbx_add_sig_shares[_d]) and the listed combines --
     @staticmethod
-    def _add_items(what: str, proposer, sender, count: int):
-        """The (proposer, sender) index arrays of an add as contiguous uint32[count]."""
+    def _index_pair(what: str, names, a, b, count: int):
+        """The two index arrays of an add's items (named `names`) as contiguous uint32[count]."""
         out = []
-        for name, a in (("proposer", proposer), ("sender", sender)):
-            a = np.asarray(a)
-            if a.ndim != 1 or a.shape[0] != count:
-                raise ValueError(f"{what}: {name} must have one entry per share ({count}), not shape {a.shape}")
-            if a.size and (a.dtype.kind not in "iu" or int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
-                raise ValueError(f"{what}: {name} must hold node / column indices (uint32)")
-            out.append(np.ascontiguousarray(a, dtype=np.uint32))
+        for name, x in zip(names, (a, b)):
+            x = np.asarray(x)
+            if x.ndim != 1 or x.shape[0] != count:
+                raise ValueError(f"{what}: {name} must have one entry per share ({count}), not shape {x.shape}")
+            if x.size and (x.dtype.kind not in "iu" or int(x.min()) < 0 or int(x.max()) > 0xFFFFFFFF):
+                raise ValueError(f"{what}: {name} must hold indices (uint32)")
+            out.append(np.ascontiguousarray(x, dtype=np.uint32))
         return out
+
+    @staticmethod
+    def _index_list(what: str, name: str, of: str, one: str, x):
+        """A list of indices, each listed once, as contiguous uint32 (`name` a list of `of`, `one` of
+        them); the library checks the bound."""
+        x = np.asarray(x)
+        if x.ndim != 1 or (x.size and (x.dtype.kind not in "iu" or int(x.min()) < 0 or int(x.max()) > 0xFFFFFFFF)):
+            raise ValueError(f"{what}: {name} must be a list of {of}")
+        if len(set(x.tolist())) != x.size:
+            raise ValueError(f"{what}: {one} is listed twice")
+        return np.ascontiguousarray(x, dtype=np.uint32)
+
+    @staticmethod
+    def _nodes(what: str, n):
+        if not isinstance(n, (int, np.integer)) or n <= 0:
+            raise ValueError(f"{what}: n must be the number of nodes")
+
+    def _add_host(self, fn: str, width: int, names, pts, a, b, n) -> np.ndarray:
+        """The host form `fn` of an add: pts uint8[count, width] and the index arrays a, b (the three
+        named `names`) -> HBX_SHARE_* uint8[count]."""
+        what = fn[4:]
+        pts = np.asarray(pts)
+        if pts.dtype != np.uint8 or pts.ndim != 2 or pts.shape[1] != width:
+            raise ValueError(f"{what}: {names[0]} must be uint8[count, {width}], not {pts.dtype}{pts.shape}")
+        pts = np.ascontiguousarray(pts)
+        count = pts.shape[0]
+        a, b = self._index_pair(what, names[1:], a, b, count)
+        self._nodes(what, n)
+        out = np.zeros(count, dtype=np.uint8)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        self._check(getattr(self.lib, fn)(
+            self.h, _u8(pts) if count else None, a.ctypes.data_as(u32p) if count else None,
+            b.ctypes.data_as(u32p) if count else None, count, int(n), _u8(out) if count else None))
+        return out
+
+    def _add_device(self, fn: str, width: int, names, d_pts, a, b, n, d_status, stream):
+        """The device form `fn` of an add: d_pts a contiguous device uint8[count, width] tensor (None
+        with no items), a / b host index arrays, d_status an optional device uint8[count].  The
+        library reads d_pts by raw pointer, so its element size and strides are checked here."""
+        what = fn[4:]
+        count = 0 if d_pts is None else int(d_pts.shape[0])
+        if d_pts is not None and (d_pts.dim() != 2 or d_pts.shape[1] != width or d_pts.element_size() != 1
+                                  or not d_pts.is_contiguous()):
+            raise ValueError(f"{what}: {names[0]} must be contiguous uint8[count, {width}], not shape {tuple(d_pts.shape)}")
+        a, b = self._index_pair(what, names[1:], a, b, count)
+        if d_status is not None and (d_status.numel() != count or d_status.element_size() != 1):
+            raise ValueError(f"{what}: d_status must have one byte per share ({count})")
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        self._check(getattr(self.lib, fn)(
+            self.h, d_pts.data_ptr() if count else None, a.ctypes.data_as(u32p) if count else None,
+            b.ctypes.data_as(u32p) if count else None, count, int(n),
+            None if d_status is None or not count else d_status.data_ptr(), self._stream(stream)))
 
     def add_dec_shares(self, shares48, proposer, sender, n: int) -> np.ndarray:
         """hbx_add_dec_shares: the shares that arrived since the last call, verified and merged into
-        the epoch's matrix.  shares48 uint8[count, 48], proposer (column j < p) and sender (node
-        index) one entry each -> HBX_SHARE_* uint8[count]."""
-        shares48 = np.ascontiguousarray(shares48, dtype=np.uint8)
-        if shares48.ndim != 2 or shares48.shape[1] != 48:
-            raise ValueError(f"add_dec_shares: shares48 must be uint8[count, 48], not shape {shares48.shape}")
-        count = shares48.shape[0]
-        prop, snd = self._add_items("add_dec_shares", proposer, sender, count)
-        if n <= 0:
-            raise ValueError("add_dec_shares: n must be the number of nodes")
-        out = np.zeros(count, dtype=np.uint8)
-        u32p = ctypes.POINTER(ctypes.c_uint32)
-        self._check(self.lib.hbx_add_dec_shares(
-            self.h, _u8(shares48) if count else None, prop.ctypes.data_as(u32p) if count else None,
-            snd.ctypes.data_as(u32p) if count else None, count, n, _u8(out) if count else None))
-        return out
+        the epoch's matrix.  shares48 uint8[count, 48] (or what converts to it), proposer (column
+        j < p) and sender (node index) one entry each -> HBX_SHARE_* uint8[count]."""
+        return self._add_host("hbx_add_dec_shares", 48, ("shares48", "proposer", "sender"),
+                              np.asarray(shares48, dtype=np.uint8), proposer, sender, n)
 
     def combine_decrypt_cols(self, t: int, cols, out=None, status=None):
         """hbx_combine_decrypt_cols: threshold decryption of the listed proposer columns only ->
         ({column: plaintext bytes or None}, {column: status}).  `out` (uint8[sum |V_j|]) and `status`
         (int32[p]), if given, are the caller's buffers: only the listed proposers' ranges and entries
         of them are written."""
-        cols = np.asarray(cols)
-        if cols.ndim != 1 or (cols.size and (cols.dtype.kind not in "iu" or int(cols.min()) < 0)):
-            raise ValueError("combine_decrypt_cols: cols must be a list of proposer columns")
+        cols = self._index_list("combine_decrypt_cols", "cols", "proposer columns", "a column", cols)
         off = self._v_off
         if off is None:  # prepared through the device API: the caller's offsets tensor
             off = self._d_off.detach().cpu().numpy().astype(np.uint64)
         p = len(off) - 1
         if cols.size and int(cols.max()) >= p:
             raise ValueError(f"combine_decrypt_cols: column {int(cols.max())} of {p} prepared ciphertexts")
-        if len(set(cols.tolist())) != cols.size:
-            raise ValueError("combine_decrypt_cols: a column is listed twice")
-        cols = np.ascontiguousarray(cols, dtype=np.uint32)
         out = np.zeros(max(int(off[-1]), 1), dtype=np.uint8) if out is None else out
         st = np.zeros(p, dtype=np.int32) if status is None else status
         if out.dtype != np.uint8 or out.size < max(int(off[-1]), 1) or not out.flags.c_contiguous or \
@@ -766,64 +817,21 @@ class Context:
         return sig, st, unpack_bits(ok, count), unpack_bits(par, count)
 
     # -- common coin, incremental ------------------------------------------------------------------
-    @staticmethod
-    def _coin_items(what: str, inst, sender, count: int, n: int):
-        """The (inst, sender) index arrays of a coin add as contiguous uint32[count]."""
-        out = []
-        for name, a in (("inst", inst), ("sender", sender)):
-            a = np.asarray(a)
-            if a.ndim != 1 or a.shape[0] != count:
-                raise ValueError(f"{what}: {name} must have one entry per share ({count}), not shape {a.shape}")
-            if a.size and (a.dtype.kind not in "iu" or int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
-                raise ValueError(f"{what}: {name} must hold instance / node indices (uint32)")
-            out.append(np.ascontiguousarray(a, dtype=np.uint32))
-        if not isinstance(n, (int, np.integer)) or n <= 0:
-            raise ValueError(f"{what}: n must be the number of nodes")
-        return out
-
-    @staticmethod
-    def _coin_insts(what: str, insts):
-        """The instance list of a listed combine as contiguous uint32[ninsts], each listed once."""
-        insts = np.asarray(insts)
-        if insts.ndim != 1 or (insts.size and (insts.dtype.kind not in "iu" or int(insts.min()) < 0
-                                               or int(insts.max()) > 0xFFFFFFFF)):
-            raise ValueError(f"{what}: insts must be a list of coin instances")
-        if len(set(insts.tolist())) != insts.size:
-            raise ValueError(f"{what}: an instance is listed twice")
-        return np.ascontiguousarray(insts, dtype=np.uint32)
+    def _coin_insts(self, what: str, insts):
+        return self._index_list(what, "insts", "coin instances", "an instance", insts)
 
     def add_sig_shares(self, sig96, inst, sender, n: int) -> np.ndarray:
         """hbx_add_sig_shares: the signature shares that arrived since the last call, verified and
         merged into the round's matrix.  sig96 uint8[count, 96], inst (< prepared nonces) and sender
         (node index) one entry each -> HBX_SHARE_* uint8[count]."""
-        sig96 = np.asarray(sig96)
-        if sig96.dtype != np.uint8 or sig96.ndim != 2 or sig96.shape[1] != 96:
-            raise ValueError(f"add_sig_shares: sig96 must be uint8[count, 96], not {sig96.dtype}{sig96.shape}")
-        sig96 = np.ascontiguousarray(sig96)
-        count = sig96.shape[0]
-        ins, snd = self._coin_items("add_sig_shares", inst, sender, count, n)
-        out = np.zeros(count, dtype=np.uint8)
-        u32p = ctypes.POINTER(ctypes.c_uint32)
-        self._check(self.lib.hbx_add_sig_shares(
-            self.h, _u8(sig96) if count else None, ins.ctypes.data_as(u32p) if count else None,
-            snd.ctypes.data_as(u32p) if count else None, count, int(n), _u8(out) if count else None))
-        return out
+        return self._add_host("hbx_add_sig_shares", 96, ("sig96", "inst", "sender"), sig96, inst, sender, n)
 
     def add_sig_shares_d(self, d_sig96, inst, sender, n: int, d_status=None, stream=None):
         """hbx_add_sig_shares_d: d_sig96 a device uint8[count, 96] tensor (None with no items), inst /
         sender host index arrays, d_status an optional device uint8[count]."""
-        count = 0 if d_sig96 is None else int(d_sig96.shape[0])
-        if d_sig96 is not None and (d_sig96.dim() != 2 or d_sig96.shape[1] != 96 or d_sig96.element_size() != 1
-                                    or not d_sig96.is_contiguous()):
-            raise ValueError(f"add_sig_shares_d: d_sig96 must be contiguous uint8[count, 96], not shape {tuple(d_sig96.shape)}")
-        ins, snd = self._coin_items("add_sig_shares_d", inst, sender, count, n)
-        if d_status is not None and (d_status.numel() != count or d_status.element_size() != 1):
-            raise ValueError(f"add_sig_shares_d: d_status must have one byte per share ({count})")
-        u32p = ctypes.POINTER(ctypes.c_uint32)
-        self._check(self.lib.hbx_add_sig_shares_d(
-            self.h, d_sig96.data_ptr() if count else None, ins.ctypes.data_as(u32p) if count else None,
-            snd.ctypes.data_as(u32p) if count else None, count, int(n),
-            None if d_status is None or not count else d_status.data_ptr(), self._stream(stream)))
+        self._nodes("add_sig_shares_d", n)
+        self._add_device("hbx_add_sig_shares_d", 96, ("d_sig96", "inst", "sender"), d_sig96, inst, sender, n, d_status,
+                         stream)
 
     def combine_signatures_insts(self, master_pk48: bytes, t: int, insts, use=None, sig=None, status=None, ok=None,
                                  parity=None):
@@ -1354,25 +1362,13 @@ class Context:
     def add_dec_shares_d(self, d_shares48, proposer, sender, n: int, d_status=None, stream=None):
         """hbx_add_dec_shares_d: d_shares48 a device uint8[count, 48] tensor (None with no items),
         proposer / sender host index arrays, d_status an optional device uint8[count]."""
-        count = 0 if d_shares48 is None else int(d_shares48.shape[0])
-        if d_shares48 is not None and (d_shares48.dim() != 2 or d_shares48.shape[1] != 48):
-            raise ValueError(f"add_dec_shares_d: d_shares48 must be uint8[count, 48], not shape {tuple(d_shares48.shape)}")
-        prop, snd = self._add_items("add_dec_shares_d", proposer, sender, count)
-        if d_status is not None and d_status.numel() != count:
-            raise ValueError(f"add_dec_shares_d: d_status must have one byte per share ({count})")
-        u32p = ctypes.POINTER(ctypes.c_uint32)
-        self._check(self.lib.hbx_add_dec_shares_d(
-            self.h, d_shares48.data_ptr() if count else None, prop.ctypes.data_as(u32p) if count else None,
-            snd.ctypes.data_as(u32p) if count else None, count, n,
-            None if d_status is None or not count else d_status.data_ptr(), self._stream(stream)))
+        self._add_device("hbx_add_dec_shares_d", 48, ("d_shares48", "proposer", "sender"), d_shares48, proposer, sender, n,
+                         d_status, stream)
 
     def combine_decrypt_cols_d(self, t: int, cols, d_out, d_status=None, stream=None):
         """hbx_combine_decrypt_cols_d: cols a host list of proposer columns; d_out / d_status as for
         combine_decrypt_d (only the listed proposers' ranges and entries are written)."""
-        cols = np.asarray(cols)
-        if cols.ndim != 1 or (cols.size and (cols.dtype.kind not in "iu" or int(cols.min()) < 0)):
-            raise ValueError("combine_decrypt_cols_d: cols must be a list of proposer columns")
-        cols = np.ascontiguousarray(cols, dtype=np.uint32)
+        cols = self._index_list("combine_decrypt_cols_d", "cols", "proposer columns", "a column", cols)
         self._check(self.lib.hbx_combine_decrypt_cols_d(
             self.h, t, cols.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if cols.size else None, cols.size,
             d_out.data_ptr(), None if d_status is None else d_status.data_ptr(), self._stream(stream)))

@@ -29,7 +29,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .hbx import CT_INVALID, CT_UNDECODABLE, CT_VALID, SHARE_INVALID, SHARE_UNDECODABLE
+from .hbx import CT_INVALID, CT_UNDECODABLE, CT_VALID, SHARE_INVALID, SHARE_UNDECODABLE, layers
 
 UNVERIFIED_DECRYPTION_SHARE_SENDER = "UnverifiedDecryptionShareSender"
 INVALID_CIPHERTEXT = "InvalidCiphertext"
@@ -308,15 +308,8 @@ class EpochSession:
     def _add_layers(self, items: List[Tuple[int, int, int, bytes]], status: Dict[int, int]):
         """items (event index, column, sender, share48) in arrival order -> one add per layer, layer
         L holding the L-th message of every pair."""
-        layers: List[List[Tuple[int, int, int, bytes]]] = []
-        seen: Dict[Tuple[int, int], int] = {}
-        for it in items:
-            L = seen.get((it[1], it[2]), 0)
-            seen[(it[1], it[2])] = L + 1
-            if L == len(layers):
-                layers.append([])
-            layers[L].append(it)
-        for layer in layers:
+        for idx in layers([(it[1], it[2]) for it in items]):
+            layer = [items[i] for i in idx]
             shares = np.frombuffer(b"".join(bytes(it[3]) for it in layer), dtype=np.uint8).reshape(len(layer), 48)
             st = self.ctx.add_dec_shares(shares, np.array([it[1] for it in layer], dtype=np.uint32),
                                          np.array([it[2] for it in layer], dtype=np.uint32), self.n)

@@ -346,3 +346,55 @@ def test_buffers_of_adds_and_listed_combines_are_freed():
         assert c.add_sig_shares(d["sigs"][0, 0:1], [0], [n + 1], n).tolist() == [UNKNOWN_SENDER]
         assert hbx.live_buffers() > start
     assert hbx.live_buffers() == start
+
+
+# ---- 9. both kinds of add on one context ----------------------------------------------------------
+def test_interleaved_decryption_and_coin_adds_equal_separate_contexts():
+    """Decryption adds and coin adds alternate on one context (each has its own add state, both pack
+    their items into the same pinned staging): per-item statuses and both matrices are what two
+    contexts leave that run one kind each.  One context holds one key set, so the coin shares are
+    signed under hb_epoch_n4's keys at coin_n4's present positions, except where coin_n4's own bytes
+    give the other statuses: its undecodable shares, and one share of its (here foreign) keys."""
+    from hbbft_amd import hbx
+
+    e, cn = _load("hb_epoch_n4"), _load("coin_n4")
+    p, n = e["shares"].shape[:2]
+    count = cn["sigs"].shape[0]
+    keys = [r.tobytes() for r in e["pk_comp"]]
+    v_off, n_off = e["v_off"], cn["nonce_off"]
+    cts = [(e["u"][j].tobytes(), e["v_blob"][int(v_off[j]):int(v_off[j + 1])].tobytes(), e["w"][j].tobytes()) for j in range(p)]
+    nonces = [cn["nonce_blob"][int(n_off[q]):int(n_off[q + 1])].tobytes() for q in range(count)]
+    dec_pos, coin_pos = np.argwhere(e["present"]), np.argwhere(cn["present"])
+    halves = {"dec": [dec_pos[0::2], dec_pos[1::2]], "coin": [coin_pos[0::2], coin_pos[1::2]]}
+    assert all(0 < len(h) < len(dec_pos) for h in halves["dec"]) and all(0 < len(h) < len(coin_pos) for h in halves["coin"])
+
+    start = hbx.live_buffers()
+    with hbx.Context(0) as dec_only, hbx.Context(0) as coin_only, hbx.Context(0) as both:
+        for c in (dec_only, coin_only, both):
+            assert (c.set_pk_shares(keys) == 0).all()
+        for c in (dec_only, both):
+            c.prepare_ciphertexts(cts)
+        for c in (coin_only, both):
+            c.prepare_nonces(nonces, hashes=False)
+        sigs = coin_only.sign(e["sk_shares"])
+        other = (cn["expect_share_status"] == UNDECODABLE) | _mask((count, n), [tuple(coin_pos[0])])
+        sigs[other] = cn["sigs"][other]
+
+        def add(ctx, kind, k):
+            pos = halves[kind][k]
+            if kind == "dec":
+                return ctx.add_dec_shares(np.ascontiguousarray(e["shares"][pos[:, 0], pos[:, 1]]), pos[:, 0], pos[:, 1], n)
+            return ctx.add_sig_shares(np.ascontiguousarray(sigs[pos[:, 0], pos[:, 1]]), pos[:, 0], pos[:, 1], n)
+
+        order = [("dec", 0), ("coin", 0), ("dec", 1), ("coin", 1)]
+        want = {(kind, k): add(dec_only if kind == "dec" else coin_only, kind, k) for kind, k in order}
+        for kind, k in order:
+            np.testing.assert_array_equal(add(both, kind, k), want[(kind, k)], err_msg=f"{kind} add {k}")
+        np.testing.assert_array_equal(both.share_status(p, n), dec_only.share_status(p, n))
+        np.testing.assert_array_equal(both.sig_share_status(count, n), coin_only.sig_share_status(count, n))
+        # the yardsticks themselves: the epoch fixture's matrix; every kind of coin status present
+        np.testing.assert_array_equal(dec_only.share_status(p, n), e["expect_share_status"])
+        coin_st = np.concatenate([want[("coin", 0)], want[("coin", 1)]])
+        assert {VALID, INVALID, UNDECODABLE} <= set(coin_st.tolist())
+        assert hbx.live_buffers() > start
+    assert hbx.live_buffers() == start

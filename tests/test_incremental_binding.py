@@ -49,6 +49,25 @@ def test_add_dec_shares_rejects_n_zero():
         _bare_context().add_dec_shares(np.zeros((1, 48), np.uint8), [0], [0], 0)
 
 
+def test_add_dec_shares_d_rejects_strided_and_wide_tensors_before_the_library():
+    """The library reads d_shares48 by raw pointer, one byte per element, rows 48 bytes apart."""
+    import torch
+
+    ctx = _bare_context()
+    strided = torch.zeros((2, 96), dtype=torch.uint8)[:, ::2]
+    transposed = torch.zeros((48, 2), dtype=torch.uint8).t()
+    wide = torch.zeros((2, 48), dtype=torch.int32)
+    for bad in (strided, transposed, wide):
+        assert tuple(bad.shape) == (2, 48)
+        with pytest.raises(ValueError, match="add_dec_shares_d: d_shares48 must be contiguous uint8"):
+            ctx.add_dec_shares_d(bad, [0, 1], [0, 1], 4)
+    with pytest.raises(ValueError, match="add_dec_shares_d: d_status must have one byte per share"):
+        ctx.add_dec_shares_d(torch.zeros((2, 48), dtype=torch.uint8), [0, 1], [0, 1], 4,
+                             d_status=torch.zeros(2, dtype=torch.int32))
+    with pytest.raises(ValueError, match="add_dec_shares_d"):
+        ctx.add_dec_shares_d(None, [0], [], 4)
+
+
 @pytest.mark.parametrize("cols", [[0, 0], [3], [-1], [[0, 1]], [0.5]])
 def test_combine_decrypt_cols_rejects_bad_columns(cols):
     with pytest.raises(ValueError, match="combine_decrypt_cols"):
