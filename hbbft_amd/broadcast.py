@@ -319,15 +319,118 @@ class BroadcastResult:
 
 
 class _Inst:
-    __slots__ = ("proposer", "echo_sent", "ready_sent", "echos", "readys", "attempts")
+    __slots__ = ("proposer", "echo_sent", "ready_sent", "decided", "echos", "readys", "attempts")
 
     def __init__(self, proposer):
         self.proposer = proposer
         self.echo_sent = False
         self.ready_sent = False
-        self.echos: Dict[int, Tuple[bytes, int]] = {}  # sender -> (root, proof id)
+        self.decided = False  # set between a session's flushes only: a replay decodes at the end
+        self.echos: Dict[int, Tuple[bytes, int]] = {}  # sender -> (root, proof id | value length)
         self.readys: Dict[int, bytes] = {}
         self.attempts: List[Tuple[int, bytes, Tuple[int, ...]]] = []  # (seq, root, senders)
+
+
+def _replay_events(events, insts, n: int, me: int, res, seq, own_proofs, ok_of, held_of):
+    """Broadcast's control flow (broadcast.rs:407-551) over ``events`` from the state in ``insts``,
+    message by message, with ``ok_of(key)`` standing in for ``validate_proof`` of event ``key``'s proof
+    (-1: our own Value) and ``held_of(key)`` -> (root, token) for what ``echos.insert`` keeps of it.
+    Faults, errors and sent messages go to ``res``; each time ``compute_output`` would decode, the
+    attempt (seq, root, Echo senders holding that root) is recorded on the instance instead.
+    ``seq``: a one-element list, the running attempt counter."""
+    f = num_faulty(n)
+    k = coding_counts(n)[0]
+
+    def count_echos(b, h):
+        return sum(1 for r, _ in b.echos.values() if r == h)
+
+    def count_readys(b, h):
+        return sum(1 for x in b.readys.values() if x == h)
+
+    def compute_output(b, h):
+        if b.decided or count_readys(b, h) <= 2 * f or count_echos(b, h) < k:
+            return
+        senders = tuple(i for i in sorted(b.echos) if b.echos[i][0] == h)
+        b.attempts.append((seq[0], h, senders))
+        seq[0] += 1
+
+    def send_ready(b, h):
+        b.ready_sent = True
+        res.sent.append((b.proposer, "ready", h))
+        handle_ready(b, me, h)
+
+    def handle_ready(b, sender, h):
+        if sender in b.readys:
+            return
+        b.readys[sender] = h
+        if count_readys(b, h) == f + 1 and not b.ready_sent:
+            send_ready(b, h)
+        compute_output(b, h)
+
+    def handle_echo(b, sender, key):
+        if sender in b.echos:
+            return
+        if not ok_of(key):
+            res.faults.append((sender, INVALID_PROOF))
+            return
+        h, token = held_of(key)
+        b.echos[sender] = (h, token)
+        if b.ready_sent or count_echos(b, h) < n - f:
+            compute_output(b, h)
+            return
+        send_ready(b, h)
+
+    def handle_value(b, sender, key):
+        if sender != b.proposer:
+            res.faults.append((sender, RECEIVED_VALUE_FROM_NON_PROPOSER))
+            return
+        if b.echo_sent:
+            return
+        if not ok_of(key):
+            res.faults.append((sender, INVALID_PROOF))
+            return
+        b.echo_sent = True  # send_echo (:494-504)
+        res.sent.append((b.proposer, "echo", held_of(key)[0]))
+        handle_echo(b, me, key)
+
+    for key, ev in enumerate(events):
+        if ev[0] == "input":
+            for i in range(n):
+                if i != me:
+                    res.sent.append((me, "value", i))
+                    res.value_proofs[i] = own_proofs[i]
+            handle_value(insts[me], me, -1)
+            continue
+        _, sender, proposer, payload = ev
+        if not 0 <= proposer < n:
+            res.errors.append((sender, NO_SUCH_BROADCAST_INSTANCE))
+            continue
+        if not 0 <= sender < n:
+            res.errors.append((sender, UNKNOWN_SENDER))
+            continue
+        b = insts[proposer]
+        if ev[0] == "value":
+            handle_value(b, sender, key)
+        elif ev[0] == "echo":
+            handle_echo(b, sender, key)
+        elif ev[0] == "ready":
+            handle_ready(b, sender, bytes(payload))
+        else:
+            raise ValueError(ev[0])
+
+
+def _ran_attempts(insts, decided):
+    """The attempts compute_output actually ran -- each instance's up to its first success
+    (``decided``: proposer -> (seq, value)) -- in the reference's order: (proposer, root, ok)."""
+    ran = []
+    for b in insts:
+        stop = decided.get(b.proposer)
+        for a in b.attempts:
+            if stop is not None and a[0] > stop[0]:
+                break
+            ran.append((a[0], b.proposer, a[1], stop is not None and a[0] == stop[0]))
+    ran.sort()
+    return [(p, h, ok) for _, p, h, ok in ran]
 
 
 class BroadcastReplay:
@@ -380,97 +483,13 @@ class BroadcastReplay:
                 res.proof_valid[w] = ok
         # 3. the control flow, message by message; decodes recorded as attempts
         insts = [_Inst(p) for p in range(n)]
-        seq = [0]
-
-        def count_echos(b, h):
-            return sum(1 for r, _ in b.echos.values() if r == h)
-
-        def count_readys(b, h):
-            return sum(1 for x in b.readys.values() if x == h)
-
-        def compute_output(b, h):
-            if count_readys(b, h) <= 2 * self.f or count_echos(b, h) < self.k:
-                return
-            senders = tuple(i for i in sorted(b.echos) if b.echos[i][0] == h)
-            b.attempts.append((seq[0], h, senders))
-            seq[0] += 1
-
-        def send_ready(b, h):
-            b.ready_sent = True
-            res.sent.append((b.proposer, "ready", h))
-            handle_ready(b, me, h)
-
-        def handle_ready(b, sender, h):
-            if sender in b.readys:
-                return
-            b.readys[sender] = h
-            if count_readys(b, h) == self.f + 1 and not b.ready_sent:
-                send_ready(b, h)
-            compute_output(b, h)
-
-        def handle_echo(b, sender, key):
-            if sender in b.echos:
-                return
-            if not ok_of[key]:
-                res.faults.append((sender, INVALID_PROOF))
-                return
-            h = bytes(proofs[pid_of[key]]["root_hash"])
-            b.echos[sender] = (h, pid_of[key])
-            if b.ready_sent or count_echos(b, h) < n - self.f:
-                compute_output(b, h)
-                return
-            send_ready(b, h)
-
-        def handle_value(b, sender, key):
-            if sender != b.proposer:
-                res.faults.append((sender, RECEIVED_VALUE_FROM_NON_PROPOSER))
-                return
-            if b.echo_sent:
-                return
-            if not ok_of[key]:
-                res.faults.append((sender, INVALID_PROOF))
-                return
-            b.echo_sent = True  # send_echo (:494-504)
-            res.sent.append((b.proposer, "echo", bytes(proofs[pid_of[key]]["root_hash"])))
-            handle_echo(b, me, key)
-
-        for k, ev in enumerate(events):
-            if ev[0] == "input":
-                for i in range(n):
-                    if i != me:
-                        res.sent.append((me, "value", i))
-                        res.value_proofs[i] = own_proofs[i]
-                handle_value(insts[me], me, -1)
-                continue
-            _, sender, proposer, payload = ev
-            if not 0 <= proposer < n:
-                res.errors.append((sender, NO_SUCH_BROADCAST_INSTANCE))
-                continue
-            if not 0 <= sender < n:
-                res.errors.append((sender, UNKNOWN_SENDER))
-                continue
-            b = insts[proposer]
-            if ev[0] == "value":
-                handle_value(b, sender, k)
-            elif ev[0] == "echo":
-                handle_echo(b, sender, k)
-            elif ev[0] == "ready":
-                handle_ready(b, sender, bytes(payload))
-            else:
-                raise ValueError(ev[0])
+        _replay_events(events, insts, n, me, res, [0], own_proofs, ok_of.__getitem__,
+                       lambda key: (bytes(proofs[pid_of[key]]["root_hash"]), pid_of[key]))
         # 4. decode waves
         decided = self._decode_waves(insts, proofs, res)
         # outputs and the attempts compute_output actually ran, in the reference's order
-        ran = []
-        for b in insts:
-            stop = decided.get(b.proposer)
-            for a in b.attempts:
-                if stop is not None and a[0] > stop[0]:
-                    break
-                ran.append((a[0], b.proposer, a[1], stop is not None and a[0] == stop[0]))
-        ran.sort()
-        res.decode_attempts = [(p, h, ok) for _, p, h, ok in ran]
-        res.outputs = [(p, decided[p][1]) for _, p, _, ok in ran if ok]
+        res.decode_attempts = _ran_attempts(insts, decided)
+        res.outputs = [(p, decided[p][1]) for p, _, ok in res.decode_attempts if ok]
         return res
 
     def _decode_waves(self, insts, proofs, res) -> Dict[int, Tuple[int, bytes]]:
@@ -504,6 +523,246 @@ class BroadcastReplay:
         for b in insts:
             for a in b.attempts:
                 v = cache[(b.proposer, a[1], a[2])]
+                if v is not None:
+                    decided[b.proposer] = (a[0], v)
+                    break
+        return decided
+
+
+# ---------------------------------------------------------------------------------------------
+# The running node: Echoes validated and stored as they arrive, listed decodes out of the store
+# ---------------------------------------------------------------------------------------------
+ECHO_INVALID, ECHO_STORED, ECHO_DUPLICATE, ECHO_OVERSIZE = 0, 1, 2, 3  # include/hbx.h HBX_ECHO_*
+
+
+class GpuBroadcastAddEngine(GpuBroadcastEngine):
+    """``GpuBroadcastEngine`` plus the echo store in the context: ``prepare`` establishes it
+    (``hbx_prepare_broadcast``), ``add`` validates arriving Echo proofs and stores the valid ones
+    (``hbx_add_echoes_d``), ``decode_listed`` decodes attempts out of the store
+    (``hbx_broadcast_decode_insts_d``).  ``value_bytes_uploaded``: the value bytes sent to the device so
+    far (adds, and the rare ``validate`` of a Value whose slot an Echo already holds); a decode
+    uploads none."""
+
+    def __init__(self, ctx, merkle_variant: int = 0, stream=None):
+        super().__init__(ctx, merkle_variant, stream, ragged=True)
+        self.value_bytes_uploaded = 0
+        self.n = 0
+
+    def prepare(self, inst: int, n: int, max_shard_len: int):
+        k, m = coding_counts(n)
+        self.ctx.prepare_broadcast(inst, k, m, max_shard_len)
+        self.n = n
+
+    def validate(self, proofs, nodes, n: int) -> np.ndarray:
+        self.value_bytes_uploaded += sum(len(p["value"]) for p in proofs)
+        return super().validate(proofs, nodes, n)
+
+    def add(self, proofs, insts, senders) -> np.ndarray:
+        """Echo proofs for slots (insts[j], senders[j]), each pair once -> HBX_ECHO_* uint8[count]."""
+        torch = self.torch
+        if not proofs:
+            return np.zeros(0, dtype=np.uint8)
+        blob, val_off, *arrs = flatten_proofs_ragged(proofs, senders)
+        self.value_bytes_uploaded += int(blob.size)
+        d_blob = self._dev(blob if blob.size else np.zeros(1, dtype=np.uint8))
+        d_nh, d_sh, d_sides, d_depth, d_root = (self._dev(a) for a in arrs[:5])
+        d_st = torch.zeros(len(proofs), dtype=torch.uint8, device=d_blob.device)
+        self.ctx.add_echoes_d(d_blob if blob.size else d_blob[:0], val_off, d_nh, d_sh, d_sides, d_depth, d_root, insts,
+                              senders, d_st, stream=self.stream)
+        return d_st.cpu().numpy()
+
+    def decode_listed(self, attempts) -> List[Optional[bytes]]:
+        """attempts: (instance, root, shard length, senders) each -> the value or None."""
+        torch = self.torch
+        na = len(attempts)
+        if na == 0:
+            return []
+        n = self.n
+        k, _ = coding_counts(n)
+        insts = np.array([a[0] for a in attempts], dtype=np.uint32)
+        roots = np.frombuffer(b"".join(bytes(a[1]) for a in attempts), dtype=np.uint8).reshape(na, 32)
+        lens = np.array([a[2] for a in attempts], dtype=np.uint32)
+        use = np.zeros((na, n), dtype=np.uint8)
+        for r, a in enumerate(attempts):
+            use[r, list(a[3])] = 1
+        room = (np.maximum(k * lens.astype(np.int64) - 4, 0) + 15) // 16 * 16
+        out_off = np.concatenate(([0], np.cumsum(room)[:-1])).astype(np.uint64)
+        dev = torch.device("cuda", self.ctx.device)
+        d_out = torch.zeros(max(int(room.sum()), 16), dtype=torch.uint8, device=dev)
+        d_len = torch.zeros(na, dtype=torch.int64, device=dev)
+        d_st = torch.zeros(na, dtype=torch.int32, device=dev)
+        self.ctx.broadcast_decode_insts_d(insts, roots, lens, d_out, out_off, d_len, d_st, use=use, n=n, stream=self.stream)
+        st, ln, ob = d_st.cpu().numpy(), d_len.cpu().numpy(), d_out.cpu().numpy()
+        return [ob[int(out_off[r]): int(out_off[r]) + int(ln[r])].tobytes() if st[r] == 0 else None for r in range(na)]
+
+
+class BroadcastSession:
+    """All N Broadcast instances of one epoch at node ``me``, fed as the messages arrive:
+    ``handle(event)`` queues an event, ``flush()`` runs the queued events and returns what they added
+    -- faults, errors, sent, outputs, decode attempts -- as a ``BroadcastResult``.  Whatever the flush
+    schedule, the results in flush order are what the reference emits message by message
+    (``oracle/broadcast.py``).
+
+    Per flush: the Echo proofs (and the proposers' Value proofs, as Echoes of ``me``) go to the
+    engine's store with one ``add`` per layer of repeated (instance, slot) pairs; Values from
+    non-proposers and malformed proofs never become items.  The control flow runs over the item
+    statuses from the state the last flush left.  The first attempt of every undecided instance is
+    decoded in one ``decode_listed``, the remaining distinct attempts of those that failed in a
+    second; an attempt equal to a failed one is not decoded again and a decided instance is never
+    listed again.  The host keeps the root and the value length of each held Echo, the device its
+    bytes.
+
+    Limit: a value longer than ``max_shard_len + 1`` bytes cannot be held (``ECHO_OVERSIZE``):
+    ``flush`` raises ``ValueError`` -- the caller's transport bound was wrong -- before it adds
+    anything, as it does for a second input; the queue and the store are then as they were.
+
+    ``engine``: a ``GpuBroadcastAddEngine``, or any object with ``prepare`` / ``send_shards`` /
+    ``validate`` / ``add`` / ``decode_listed`` (tests)."""
+
+    def __init__(self, engine, n: int, me: int, max_shard_len: int):
+        self.engine = engine
+        self.n = n
+        self.me = me
+        self.max_shard_len = max_shard_len
+        self.engine_adds = 0     # engine add calls so far (one per layer per flush)
+        self.engine_decodes = 0  # attempts the engine decoded so far
+        self._queue: List[tuple] = []
+        self._insts = [_Inst(p) for p in range(n)]
+        self._seq = [0]
+        self._known: Dict[Tuple[int, bytes, Tuple[int, ...]], Optional[bytes]] = {}
+        self._had_input = False
+        engine.prepare(n, n, max_shard_len)
+
+    def handle(self, event):
+        if event[0] not in ("input", "value", "echo", "ready"):
+            raise ValueError(event[0])
+        self._queue.append(event)
+
+    def flush(self) -> BroadcastResult:
+        # what a flush refuses it refuses before it takes anything: the queue and the store stay as
+        # they are, and the caller may drop the offending message and flush again
+        events = self._queue
+        n, me = self.n, self.me
+        inputs = [k for k, ev in enumerate(events) if ev[0] == "input"]
+        if len(inputs) > 1 or (inputs and self._had_input):
+            raise ValueError("one input per Broadcast instance")
+        k_data = coding_counts(n)[0]
+        if any(-(-(len(ev[1]) + 4) // k_data) > self.max_shard_len for ev in events if ev[0] == "input") or \
+                any(len(ev[3]["value"]) > self.max_shard_len + 1 for ev in events if self._is_item(ev)):
+            raise ValueError(f"a value is longer than max_shard_len + 1 = {self.max_shard_len + 1} bytes")
+        self._queue = []
+        res = BroadcastResult(proof_valid=[None] * len(events))
+        own_proofs = None
+        if inputs:
+            self._had_input = True
+            own_proofs = self.engine.send_shards(bytes(events[inputs[0]][1]), n)
+        # the items of this flush: (event key, proof, instance, slot)
+        items = []
+        for key, ev in enumerate(events):
+            if ev[0] == "input":
+                items.append((-1, own_proofs[me], me, me))
+            elif self._is_item(ev):
+                _, sender, proposer, p = ev
+                items.append((key, p, proposer, me if ev[0] == "value" else sender))
+        status = self._add(items)
+        st_of = {it[0]: int(status[q]) for q, it in enumerate(items)}
+        proof_of = {it[0]: it[1] for it in items}
+        assert ECHO_OVERSIZE not in st_of.values()  # refused above
+        # DUPLICATE says nothing about the proof; the control flow asks only in one corner (a Value
+        # whose slot an Echo claiming our id already holds): those are validated apart, and it runs again
+        extra: Dict[int, bool] = {}
+        while True:
+            need: List[int] = []
+
+            def ok_of(key):
+                st = st_of.get(key, ECHO_INVALID)
+                if st == ECHO_DUPLICATE:
+                    if key not in extra:
+                        need.append(key)
+                        return False
+                    return extra[key]
+                return st == ECHO_STORED
+
+            insts = [self._copy(b) for b in self._insts]
+            seq = [self._seq[0]]
+            run = BroadcastResult()
+            _replay_events(events, insts, n, me, run, seq, own_proofs, ok_of,
+                           lambda key: (bytes(proof_of[key]["root_hash"]), len(proof_of[key]["value"])))
+            if not need:
+                break
+            keys = list(dict.fromkeys(need))
+            got = self.engine.validate([proof_of[q] for q in keys], [me if q < 0 or events[q][0] == "value" else events[q][1]
+                                                                     for q in keys], n)
+            extra.update({q: bool(v) for q, v in zip(keys, got)})
+        self._seq = seq
+        res.faults, res.errors, res.sent, res.value_proofs = run.faults, run.errors, run.sent, run.value_proofs
+        for key, st in st_of.items():
+            if key >= 0:
+                res.proof_valid[key] = extra.get(key) if st == ECHO_DUPLICATE else st == ECHO_STORED
+        decided = self._decode_waves(insts, res)
+        res.decode_attempts = _ran_attempts(insts, decided)
+        res.outputs = [(p, decided[p][1]) for p, _, ok in res.decode_attempts if ok]
+        for b in insts:
+            b.attempts = []
+            b.decided = b.decided or b.proposer in decided
+        self._insts = insts
+        return res
+
+    def _is_item(self, ev) -> bool:
+        """A Value from its proposer or an Echo, of known nodes, with a well-formed proof."""
+        if ev[0] not in ("value", "echo"):
+            return False
+        _, sender, proposer, p = ev
+        return 0 <= proposer < self.n and 0 <= sender < self.n and (ev[0] == "echo" or sender == proposer) \
+            and proof_shape_ok(p)
+
+    @staticmethod
+    def _copy(b: "_Inst") -> "_Inst":
+        c = _Inst(b.proposer)
+        c.echo_sent, c.ready_sent, c.decided = b.echo_sent, b.ready_sent, b.decided
+        c.echos, c.readys = dict(b.echos), dict(b.readys)
+        return c
+
+    def _add(self, items) -> np.ndarray:
+        """One engine add per layer (layer L = the L-th item of each (instance, slot) pair in this
+        flush), in order, so the store ends as message-by-message delivery leaves it."""
+        from .hbx import layers
+
+        status = np.zeros(len(items), dtype=np.uint8)
+        for layer in layers([it[2:] for it in items]):
+            status[layer] = self.engine.add([items[q][1] for q in layer], [items[q][2] for q in layer],
+                                            [items[q][3] for q in layer])
+            self.engine_adds += 1
+        return status
+
+    def _decode_waves(self, insts, res) -> Dict[int, Tuple[int, bytes]]:
+        """proposer -> (seq of the first successful attempt, value), over this flush's attempts."""
+
+        def shard_len(b, senders):
+            return b.echos[senders[0]][1] - 1  # value length without the index byte
+
+        def run(batch):
+            todo = [key for key in dict.fromkeys(batch) if key not in self._known]
+            # leaves that are only the index byte glue fewer than 4 bytes: None (broadcast.rs:697-707)
+            for key in [key for key in todo if shard_len(insts[key[0]], key[2]) < 1]:
+                self._known[key] = None
+            todo = [key for key in todo if key not in self._known]
+            if todo:
+                got = self.engine.decode_listed([(p, h, shard_len(insts[p], s), s) for p, h, s in todo])
+                self.engine_decodes += len(todo)
+                res.engine_decodes += len(todo)
+                for key, v in zip(todo, got):
+                    self._known[key] = v
+
+        first = [(b.proposer, b.attempts[0][1], b.attempts[0][2]) for b in insts if b.attempts]
+        run(first)
+        rest = [(b.proposer, a[1], a[2]) for b in insts
+                if b.attempts and self._known[(b.proposer,) + b.attempts[0][1:]] is None for a in b.attempts[1:]]
+        run(rest)
+        decided = {}
+        for b in insts:
+            for a in b.attempts:
+                v = self._known[(b.proposer, a[1], a[2])]
                 if v is not None:
                     decided[b.proposer] = (a[0], v)
                     break

@@ -1682,4 +1682,195 @@ __global__ void k_root_check(const uint8_t* __restrict__ roots, const uint8_t* _
 }
 #endif
 
+// ---------------------------------------------------------------------------------------------
+// The echo store (include/hbx.h hbx_prepare_broadcast): the first validated Echo value of every
+// (instance, sender), kept on the device from its arrival to the instance's decode.  Slot
+// s = inst * n + sender: state[s] (0 empty, 1 held), len[s] (shard bytes, without the index byte),
+// the shard at shard + s * pitch (pitch = max_shard_len rounded up to 4), root[s][32] and
+// leaf[s][32] (the proof's root and leaf digest, bytes as on the wire).
+// An add (hbx_add_echoes_d) is k_echo_precheck -> k_echo_values_* -> k_echo_validate ->
+// k_echo_store over item status bytes; a listed decode (hbx_broadcast_decode_insts_d) copies what
+// it needs out of the store (k_echo_gather) and never writes it.
+// ---------------------------------------------------------------------------------------------
+constexpr uint8_t ECHO_INVALID = 0, ECHO_STORED = 1, ECHO_DUPLICATE = 2, ECHO_OVERSIZE = 3;
+constexpr uint8_t ECHO_PENDING = 0xFF;  // between the precheck and the validation of one add
+constexpr uint32_t ECHO_COPY = 16;      // bytes per thread of the store and gather copies
+
+#if HBX_IN_TU(6)
+// Item j = (inst, sender): DUPLICATE if its slot is held (the value is not looked at: handle_echo
+// returns before validate_proof, broadcast.rs:441-448), OVERSIZE if its shard cannot fit a row,
+// else PENDING.
+__global__ void __launch_bounds__(64) k_echo_precheck(const uint2* __restrict__ items,
+                                                      const uint64_t* __restrict__ val_off, uint32_t count,
+                                                      uint32_t n, uint32_t max_shard_len,
+                                                      const uint8_t* __restrict__ state, uint8_t* __restrict__ st) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= count) return;
+  const uint64_t vlen = val_off[j + 1] - val_off[j];
+  const size_t slot = (size_t)items[j].x * n + items[j].y;
+  st[j] = state[slot] ? ECHO_DUPLICATE : vlen > (uint64_t)max_shard_len + 1 ? ECHO_OVERSIZE : ECHO_PENDING;
+}
+
+// k_merkle_values_sha256_rg / k_merkle_values_sha3_rg for the PENDING items of an add: a block whose
+// items are all decided hashes nothing.  The SHA-256 block's idle lanes hash along on the block's
+// first value (readable whatever its status).
+__global__ void __launch_bounds__(128) k_echo_values_sha256(const uint8_t* __restrict__ values,
+                                                            const uint64_t* __restrict__ val_off,
+                                                            const uint32_t* __restrict__ vlen,
+                                                            const uint32_t* __restrict__ idx,
+                                                            const uint8_t* __restrict__ st,
+                                                            uint32_t* __restrict__ digest) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t j = idx[(size_t)blockIdx.x * 64 + lane];
+  const bool live = j != VAL_NONE && st[j] == ECHO_PENDING;
+  if (!__syncthreads_or(live ? 1 : 0)) return;
+  const uint32_t jr = live ? j : idx[(size_t)blockIdx.x * 64];
+  const uint8_t* data = values + val_off[jr] + 1;
+  merkle_leaves_sha256_block(data, (uint32_t)data[-1] << 8, ld_uniform(&vlen[blockIdx.x]) - 1, live,
+                             digest + (size_t)jr * 8);
+}
+
+__global__ void __launch_bounds__(64) k_echo_values_sha3(const uint8_t* __restrict__ values,
+                                                         const uint64_t* __restrict__ val_off,
+                                                         const uint32_t* __restrict__ vlen,
+                                                         const uint32_t* __restrict__ idx,
+                                                         const uint8_t* __restrict__ st, uint32_t* __restrict__ digest) {
+  const uint32_t lane = threadIdx.x, h = lane & 1u;
+  const uint32_t j = idx[(size_t)blockIdx.x * 32 + (lane >> 1)];
+  if (j == VAL_NONE || st[j] != ECHO_PENDING) return;  // whole pairs
+  const uint8_t* data = values + val_off[j] + 1;
+  merkle_leaf_sha3_pair(data, (uint32_t)data[-1], ld_uniform(&vlen[blockIdx.x]) - 1, h, digest + (size_t)j * 8);
+}
+
+// validate_proof of the PENDING items, as k_merkle_validate_rg decides it: STORED or INVALID.
+__global__ void __launch_bounds__(64) k_echo_validate(const uint8_t* __restrict__ values,
+                                                      const uint64_t* __restrict__ val_off,
+                                                      const uint8_t* __restrict__ node_hash,
+                                                      const uint8_t* __restrict__ sib_hash,
+                                                      const uint32_t* __restrict__ sides,
+                                                      const uint32_t* __restrict__ depth,
+                                                      const uint8_t* __restrict__ root_hash,
+                                                      const uint32_t* __restrict__ sender, uint32_t n, uint32_t count,
+                                                      uint8_t* __restrict__ st, int variant,
+                                                      const uint32_t* __restrict__ vdigest) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= count || st[j] != ECHO_PENDING) return;
+  const uint64_t o0 = val_off[j];
+  const uint32_t vlen = (uint32_t)(val_off[j + 1] - o0);
+  merkle_validate_one(values + o0, vlen, j, node_hash, sib_hash, sides, depth, root_hash, sender, n, st, variant,
+                      vlen > 256 ? vdigest : nullptr);  // writes st[j] = 1 (ECHO_STORED) or 0 (ECHO_INVALID)
+}
+
+// The STORED items into their slots.  grid (ceil(max shard / (256 * ECHO_COPY)), count): block x
+// of item j copies shard bytes [x * 4096, +4096), thread = ECHO_COPY bytes: four dword stores into
+// the (dword-aligned) row from five aligned source dwords funnelled by the source's byte offset,
+// bytes at the shard's end.  Block 0 writes the slot's length, root, leaf digest and state, after
+// its bytes.
+__global__ void __launch_bounds__(256) k_echo_store(const uint8_t* __restrict__ values,
+                                                    const uint64_t* __restrict__ val_off,
+                                                    const uint2* __restrict__ items,
+                                                    const uint8_t* __restrict__ node_hash,
+                                                    const uint32_t* __restrict__ depth,
+                                                    const uint8_t* __restrict__ root_hash,
+                                                    const uint8_t* __restrict__ st, uint32_t n, uint32_t pitch,
+                                                    uint8_t* __restrict__ shard, uint32_t* __restrict__ slot_len,
+                                                    uint8_t* __restrict__ slot_root, uint8_t* __restrict__ slot_leaf,
+                                                    uint8_t* __restrict__ state) {
+  const uint32_t j = blockIdx.y;
+  if (st[j] != ECHO_STORED) return;
+  const uint64_t o0 = val_off[j];
+  const uint32_t L = (uint32_t)(val_off[j + 1] - o0) - 1;  // a STORED value holds the index byte: 1 <= vlen <= pitch + 1
+  const size_t slot = (size_t)items[j].x * n + items[j].y;
+  const uint8_t* src = values + o0 + 1;
+  uint8_t* dst = shard + slot * pitch;
+  const uint32_t q0 = (blockIdx.x * blockDim.x + threadIdx.x) * ECHO_COPY;
+  if (q0 < L) {
+    const uint8_t* sp = src + q0;
+    if (q0 + ECHO_COPY + 4 <= L) {  // the fifth source dword ends within the shard
+      const uint32_t sh = (uint32_t)((uintptr_t)sp & 3);
+      const uint32_t* s4 = reinterpret_cast<const uint32_t*>((uintptr_t)sp & ~(uintptr_t)3);
+      const uint32_t a0 = s4[0], a1 = s4[1], a2 = s4[2], a3 = s4[3], a4 = sh ? s4[4] : 0u;
+      uint32_t* d4 = reinterpret_cast<uint32_t*>(dst + q0);
+      d4[0] = __builtin_amdgcn_alignbyte(a1, a0, sh);
+      d4[1] = __builtin_amdgcn_alignbyte(a2, a1, sh);
+      d4[2] = __builtin_amdgcn_alignbyte(a3, a2, sh);
+      d4[3] = __builtin_amdgcn_alignbyte(a4, a3, sh);
+    } else {
+      const uint32_t end = L - q0 < ECHO_COPY ? L - q0 : ECHO_COPY;
+      for (uint32_t b = 0; b < end; b++) dst[q0 + b] = sp[b];
+    }
+  }
+  if (blockIdx.x != 0) return;
+  if (threadIdx.x < 32) {
+    slot_root[slot * 32 + threadIdx.x] = root_hash[(size_t)j * 32 + threadIdx.x];
+  } else if (threadIdx.x < 64) {
+    const uint32_t b = threadIdx.x - 32;
+    slot_leaf[slot * 32 + b] = node_hash[((size_t)j * 17 + depth[j]) * 32 + b];
+  } else if (threadIdx.x == 64) {
+    slot_len[slot] = L;
+    state[slot] = 1;
+  }
+}
+
+// Attempt a of a listed decode = (instance insts[a], root roots[a], shard length desc[a].len, the
+// senders use[a][n]): shard i is present iff use allows it, the slot is held and its root is the
+// attempt's.  grid (ceil(max len / (256 * ECHO_COPY)), n, attempts): the present rows into the work
+// buffer at desc[a] (rows are 16-byte aligned there, dword-aligned in the store); block x = 0 writes
+// present[a][i] and the row's leaf digest, and flags the attempt when a present row's length is not
+// the attempt's (size_bad[a] = 1: reed-solomon-erasure's IncorrectShardSize).  Reads the store only.
+__global__ void __launch_bounds__(256) k_echo_gather(const uint32_t* __restrict__ insts,
+                                                     const uint8_t* __restrict__ roots,
+                                                     const uint8_t* __restrict__ use, const rg_desc* __restrict__ desc,
+                                                     uint32_t n, uint32_t pitch, const uint8_t* __restrict__ shard,
+                                                     const uint32_t* __restrict__ slot_len,
+                                                     const uint8_t* __restrict__ slot_root,
+                                                     const uint8_t* __restrict__ slot_leaf,
+                                                     const uint8_t* __restrict__ state, uint8_t* __restrict__ work,
+                                                     uint8_t* __restrict__ present, uint8_t* __restrict__ leaf,
+                                                     uint32_t* __restrict__ size_bad) {
+  const uint32_t a = blockIdx.z, i = blockIdx.y;
+  const size_t slot = (size_t)insts[a] * n + i, w = (size_t)a * n + i;
+  bool have = use[w] != 0 && state[slot] != 0;
+  if (have) {
+    const uint32_t* r = reinterpret_cast<const uint32_t*>(slot_root + slot * 32);
+    const uint8_t* e = roots + (size_t)a * 32;  // staged at a byte offset: compared by bytes
+    for (int q = 0; q < 8 && have; q++) {
+      const uint32_t want = (uint32_t)e[4 * q] | ((uint32_t)e[4 * q + 1] << 8) | ((uint32_t)e[4 * q + 2] << 16) |
+                            ((uint32_t)e[4 * q + 3] << 24);
+      have = r[q] == want;
+    }
+  }
+  const uint32_t L = ld_uniform(&desc[a].len);
+  const bool fits = have && slot_len[slot] == L;
+  if (blockIdx.x == 0) {
+    if (threadIdx.x == 0) {
+      present[w] = have ? 1 : 0;
+      if (have && !fits) size_bad[a] = 1;
+    }
+    if (have && threadIdx.x < 32) leaf[w * 32 + threadIdx.x] = slot_leaf[slot * 32 + threadIdx.x];
+  }
+  if (!fits) return;
+  const uint32_t q0 = (blockIdx.x * blockDim.x + threadIdx.x) * ECHO_COPY;
+  if (q0 >= L) return;
+  const uint8_t* src = shard + slot * pitch + q0;
+  uint8_t* dst = work + ld_uniform(&desc[a].off) + (size_t)i * ld_uniform(&desc[a].pitch) + q0;
+  if (q0 + ECHO_COPY <= L) {
+    const uint32_t* s4 = reinterpret_cast<const uint32_t*>(src);
+    const uint32_t v0 = s4[0], v1 = s4[1], v2 = s4[2], v3 = s4[3];
+    *reinterpret_cast<uint4*>(dst) = make_uint4(v0, v1, v2, v3);
+  } else {
+    for (uint32_t b = 0; b < L - q0; b++) dst[b] = src[b];
+  }
+}
+
+// After the reconstruct set-up wrote the attempts' statuses: a flagged attempt gets `code`
+// (HBX_E_SHARD_SIZE), whatever the set-up found (the crate checks the shard sizes before it counts
+// the shards).
+__global__ void k_echo_size_status(const uint32_t* __restrict__ size_bad, uint32_t na, int32_t code,
+                                   int32_t* __restrict__ status) {
+  const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
+  if (a < na && size_bad[a]) status[a] = code;
+}
+#endif
+
 }  // namespace hbx

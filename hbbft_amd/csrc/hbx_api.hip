@@ -18,6 +18,7 @@
 #include "hbx_kernels.hip"
 #include "broadcast.hpp"
 #include "addplan.hpp"
+#include "bcplan.hpp"
 #if defined(HBX_TU) && HBX_TU == 0
 #include "_kdecl.hpp"  // the kernels live in translation units 1..6 (tools/build.py)
 #endif
@@ -245,6 +246,16 @@ struct hbx_ctx {
   dbuf rg_dev;
   pinbuf rg_pin;
   dev_event rg_ev;
+  // the echo store (hbx_prepare_broadcast): bc_live = the slots belong to (bc_inst, bc_k, bc_m,
+  // bc_max) and the current Merkle digest (hbx_set_merkle_digest clears it).  Per slot inst * n +
+  // sender: a state byte, the shard length, the shard row (bc_pitch = bc_max rounded up to 4; one
+  // canary row follows the last slot's), the proof's root and its leaf digest.  bc_item_st: an add's
+  // item statuses when the caller takes none.  A listed decode's work: the gathered rows, their
+  // presence and leaf digests, the attempts' shard-size flags.
+  bool bc_live = false;
+  uint32_t bc_inst = 0, bc_k = 0, bc_m = 0, bc_max = 0, bc_pitch = 0;
+  dbuf bc_state, bc_len, bc_shard, bc_root, bc_leaf, bc_item_st;
+  dbuf bc_work, bc_present, bc_leaf_w, bc_size_bad;
   // common coin state: nonces' hash_g2 points and lines, signature shares, combined signatures
   uint32_t coin_I = 0, coin_n = 0;
   dbuf coin_blob, coin_off, coin_H, coin_Hp, coin_lines, coin_scratch, coin_sk, coin_sig96, coin_sig, coin_sig_st, coin_present,
@@ -849,6 +860,7 @@ int hbx_set_merkle_digest(hbx_ctx* c, int variant) {
   if (!c || (variant != HBX_MERKLE_SHA256 && variant != HBX_MERKLE_SHA3))
     return fail(c, HBX_E_INVALID_ARG, "hbx_set_merkle_digest: unknown variant %d", variant);
   c->merkle = variant;
+  c->bc_live = false;  // the held Echo values were validated under the previous digest
   return HBX_OK;
 }
 
@@ -1976,6 +1988,276 @@ int hbx_broadcast_decode_leaves(hbx_ctx* c, uint8_t* shards, const uint8_t* pres
   if (!leaf_hash) return fail(c, HBX_E_INVALID_ARG, "hbx_broadcast_decode_leaves: leaf_hash is NULL");
   return broadcast_decode_host(c, shards, present, leaf_hash, root_expect, inst, k, m, L, out, out_stride, out_len,
                                status, "hbx_broadcast_decode_leaves");
+}
+// ---- Broadcast, message by message (include/hbx.h): the echo store, adds and listed decodes -----
+int hbx_prepare_broadcast(hbx_ctx* c, uint32_t inst, uint32_t k, uint32_t m, uint32_t max_shard_len) {
+  const char* fn = "hbx_prepare_broadcast";
+  if (!c || inst == 0 || max_shard_len == 0 || max_shard_len > 0xFFFFFFF0u)
+    return fail(c, HBX_E_INVALID_ARG, "%s: bad args", fn);
+  if (k == 0 || k > (uint32_t)RS_MAX_K || k + m > (uint32_t)RS_MAX_N)
+    return fail(c, HBX_E_INVALID_ARG, "rs: need 1 <= k <= %d and k + m <= %d (k=%u m=%u)", RS_MAX_K, RS_MAX_N, k, m);
+  HBX_ENTER(c, c->stream);
+  const size_t slots = (size_t)inst * (k + m);
+  const uint32_t pitch = (max_shard_len + 3) & ~3u;
+  const bool same = c->bc_state.p && c->bc_inst == inst && c->bc_k == k && c->bc_m == m && c->bc_max == max_shard_len;
+  c->bc_live = false;
+  if (!same) {
+    if (!c->bc_state.ensure(slots) || !c->bc_len.ensure(slots * 4) || !c->bc_shard.ensure((slots + 1) * pitch) ||
+        !c->bc_root.ensure(slots * 32) || !c->bc_leaf.ensure(slots * 32))
+      return fail(c, HBX_E_OUT_OF_MEMORY, "%s: out of device memory (%zu slots of %u bytes)", fn, slots, pitch);
+    c->bc_inst = inst, c->bc_k = k, c->bc_m = m, c->bc_max = max_shard_len, c->bc_pitch = pitch;
+    HIPCHK(c, hipMemsetAsync(c->bc_len.p, 0, slots * 4, s));
+    HIPCHK(c, hipMemsetAsync(c->bc_root.p, 0, slots * 32, s));
+    HIPCHK(c, hipMemsetAsync(c->bc_shard.as<uint8_t>() + slots * pitch, 0xA5, pitch, s));  // the canary row
+  }
+  HIPCHK(c, hipMemsetAsync(c->bc_state.p, 0, slots, s));
+  c->bc_live = true;
+  return HBX_OK;
+}
+
+static int bc_plan_rejected(hbx_ctx* c, int rc, const char* fn) {
+  switch (rc) {
+    case hbx_bcplan::PLAN_BAD_INST:
+      return fail(c, HBX_E_INVALID_ARG, "%s: an instance is not below the store's %u", fn, c->bc_inst);
+    case hbx_bcplan::PLAN_BAD_SENDER:
+      return fail(c, HBX_E_INVALID_ARG, "%s: a sender is not below n = %u", fn, c->bc_k + c->bc_m);
+    case hbx_bcplan::PLAN_DUPLICATE:
+      return fail(c, HBX_E_INVALID_ARG, "%s: the same entry twice in one call", fn);
+    case hbx_bcplan::PLAN_BAD_OFFSETS:
+      return fail(c, HBX_E_INVALID_ARG, "%s: val_off is not a non-decreasing offset list within the values", fn);
+    case hbx_bcplan::PLAN_BAD_LEN:
+      return fail(c, HBX_E_INVALID_ARG, "%s: need 1 <= len <= max_shard_len = %u", fn, c->bc_max);
+    case hbx_bcplan::PLAN_NO_ROOM:
+      return fail(c, HBX_E_INVALID_ARG, "%s: an attempt has no room of its own for k len - 4 output bytes", fn);
+    default:
+      return HBX_OK;
+  }
+}
+
+int hbx_add_echoes_d(hbx_ctx* c, const uint8_t* d_values, uint64_t values_bytes, const uint64_t* val_off,
+                     const uint8_t* d_node_hash, const uint8_t* d_sib_hash, const uint32_t* d_sides,
+                     const uint32_t* d_depth, const uint8_t* d_root, const uint32_t* inst, const uint32_t* sender,
+                     uint32_t count, uint8_t* d_status, void* stream) {
+  const char* fn = "hbx_add_echoes_d";
+  if (!c) return HBX_E_INVALID_ARG;
+  if (!c->bc_live) return fail(c, HBX_E_NO_BROADCAST, "%s: no echo store (hbx_prepare_broadcast)", fn);
+  if (count == 0) return HBX_OK;
+  if (!d_values || !val_off || !d_node_hash || !d_sib_hash || !d_sides || !d_depth || !d_root || !inst || !sender)
+    return fail(c, HBX_E_INVALID_ARG, "%s: bad args", fn);
+  const uint32_t n = c->bc_k + c->bc_m;
+  if (int rc = hbx_bcplan::check_items(inst, sender, count, n, c->bc_inst)) return bc_plan_rejected(c, rc, fn);
+  if (int rc = hbx_bcplan::check_offsets(val_off, count, values_bytes)) return bc_plan_rejected(c, rc, fn);
+  HBX_ENTER(c, stream);
+  const uint32_t B = c->merkle == HBX_MERKLE_SHA256 ? 64 : 32;
+  std::vector<uint32_t> blk_len, blk_idx;
+  hbx_bcplan::group_long(val_off, count, B, (uint64_t)c->bc_max + 1, blk_len, blk_idx);
+  const size_t nblk = blk_len.size();
+  // staging: val_off u64[count + 1] | items uint2[count] | sender u32[count] | blk_len | blk_idx
+  const size_t o_items = (size_t)(count + 1) * 8, o_snd = o_items + (size_t)count * 8,
+               o_len = (o_snd + (size_t)count * 4 + 7) & ~(size_t)7, o_idx = o_len + ((nblk * 4 + 7) & ~(size_t)7),
+               bytes = o_idx + nblk * B * 4;
+  uint8_t* h = staging_begin(c, bytes);
+  if (!h || (nblk && !c->val_digest.ensure((size_t)count * 32)) || (!d_status && !c->bc_item_st.ensure(count)))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "%s: out of memory", fn);
+  memcpy(h, val_off, o_items);
+  uint2* it = reinterpret_cast<uint2*>(h + o_items);
+  for (uint32_t j = 0; j < count; j++) it[j] = make_uint2(inst[j], sender[j]);
+  memcpy(h + o_snd, sender, (size_t)count * 4);
+  if (nblk) {
+    memcpy(h + o_len, blk_len.data(), nblk * 4);
+    memcpy(h + o_idx, blk_idx.data(), nblk * B * 4);
+  }
+  if (int rc = staging_upload(c, bytes, s)) return rc;
+  const uint8_t* dv = c->rg_dev.as<uint8_t>();
+  const uint64_t* d_off = reinterpret_cast<const uint64_t*>(dv);
+  const uint2* d_items = reinterpret_cast<const uint2*>(dv + o_items);
+  uint8_t* st = d_status ? d_status : c->bc_item_st.as<uint8_t>();
+  hipLaunchKernelGGL(k_echo_precheck, dim3((count + 63) / 64), dim3(64), 0, s, d_items, d_off, count, n, c->bc_max,
+                     c->bc_state.as<uint8_t>(), st);
+  if (nblk) {
+    timed t_(c, HBX_K_MERKLE_LEAVES, s);
+    if (c->merkle == HBX_MERKLE_SHA256)
+      hipLaunchKernelGGL(k_echo_values_sha256, dim3((unsigned)nblk), dim3(128), 0, s, d_values, d_off,
+                         reinterpret_cast<const uint32_t*>(dv + o_len), reinterpret_cast<const uint32_t*>(dv + o_idx), st,
+                         c->val_digest.as<uint32_t>());
+    else
+      hipLaunchKernelGGL(k_echo_values_sha3, dim3((unsigned)nblk), dim3(64), 0, s, d_values, d_off,
+                         reinterpret_cast<const uint32_t*>(dv + o_len), reinterpret_cast<const uint32_t*>(dv + o_idx), st,
+                         c->val_digest.as<uint32_t>());
+  }
+  hipLaunchKernelGGL(k_echo_validate, dim3((count + 63) / 64), dim3(64), 0, s, d_values, d_off, d_node_hash, d_sib_hash,
+                     d_sides, d_depth, d_root, reinterpret_cast<const uint32_t*>(dv + o_snd), n, count, st, c->merkle,
+                     c->val_digest.as<uint32_t>());
+  // the longest value that can be stored bounds the copy grid; shorter items' spare blocks return at once
+  uint64_t longest = 0;
+  for (uint32_t j = 0; j < count; j++) {
+    const uint64_t v = val_off[j + 1] - val_off[j];
+    if (v <= (uint64_t)c->bc_max + 1 && v > longest) longest = v;
+  }
+  const uint32_t per_block = 256 * ECHO_COPY;
+  const uint32_t xb = longest > 1 ? (uint32_t)((longest - 1 + per_block - 1) / per_block) : 1;
+  for (uint32_t j0 = 0; j0 < count; j0 += 65535) {  // grid.y limit
+    const uint32_t cnt = count - j0 < 65535 ? count - j0 : 65535;
+    hipLaunchKernelGGL(k_echo_store, dim3(xb, cnt), dim3(256), 0, s, d_values, d_off + j0, d_items + j0,
+                       d_node_hash + (size_t)j0 * 17 * 32, d_depth + j0, d_root + (size_t)j0 * 32, st + j0, n, c->bc_pitch,
+                       c->bc_shard.as<uint8_t>(), c->bc_len.as<uint32_t>(), c->bc_root.as<uint8_t>(),
+                       c->bc_leaf.as<uint8_t>(), c->bc_state.as<uint8_t>());
+  }
+  HIPCHK(c, hipGetLastError());
+  return HBX_OK;
+}
+
+int hbx_add_echoes(hbx_ctx* c, const uint8_t* values, uint64_t values_bytes, const uint64_t* val_off,
+                   const uint8_t* node_hash, const uint8_t* sib_hash, const uint32_t* sides, const uint32_t* depth,
+                   const uint8_t* root, const uint32_t* inst, const uint32_t* sender, uint32_t count, uint8_t* status) {
+  const char* fn = "hbx_add_echoes";
+  if (!c) return HBX_E_INVALID_ARG;
+  if (!c->bc_live) return fail(c, HBX_E_NO_BROADCAST, "%s: no echo store (hbx_prepare_broadcast)", fn);
+  if (count == 0) return HBX_OK;
+  if (!values || !val_off || !node_hash || !sib_hash || !sides || !depth || !root || !inst || !sender)
+    return fail(c, HBX_E_INVALID_ARG, "%s: bad args", fn);
+  if (int rc = hbx_bcplan::check_offsets(val_off, count, values_bytes)) return bc_plan_rejected(c, rc, fn);
+  HBX_ENTER(c, c->stream);
+  const size_t P = count;
+  HBX_STAGE(dv, 0, values_bytes, fn);
+  HBX_STAGE(dh, 1, P * 17 * 32, fn);
+  HBX_STAGE(dsib, 2, P * 16 * 32, fn);
+  HBX_STAGE(du, 3, P * 8, fn);  // sides | depth
+  HBX_STAGE(dr, 4, P * 32, fn);
+  HBX_STAGE(dst, 5, P, fn);
+  if (values_bytes) HBX_H2D(dv, values, values_bytes);
+  HBX_H2D(dh, node_hash, P * 17 * 32);
+  HBX_H2D(dsib, sib_hash, P * 16 * 32);
+  HBX_H2D(du, sides, P * 4);
+  HBX_H2D(du + P * 4, depth, P * 4);
+  HBX_H2D(dr, root, P * 32);
+  const uint32_t* u = (const uint32_t*)du;
+  if (int rc = hbx_add_echoes_d(c, dv, values_bytes, val_off, dh, dsib, u, u + P, dr, inst, sender, count, dst, c->stream))
+    return rc;
+  std::vector<uint8_t> got(P);
+  HBX_D2H(got.data(), dst, P);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (status) memcpy(status, got.data(), P);
+  return HBX_OK;
+}
+
+int hbx_broadcast_decode_insts_d(hbx_ctx* c, const uint32_t* insts, const uint8_t* roots, const uint32_t* len,
+                                 const uint8_t* use, uint32_t na, uint8_t* d_out, uint64_t out_bytes,
+                                 const uint64_t* out_off, uint64_t* d_out_len, int32_t* d_status, void* stream) {
+  const char* fn = "hbx_broadcast_decode_insts_d";
+  if (!c) return HBX_E_INVALID_ARG;
+  if (!c->bc_live) return fail(c, HBX_E_NO_BROADCAST, "%s: no echo store (hbx_prepare_broadcast)", fn);
+  if (na == 0) return HBX_OK;
+  if (!insts || !roots || !len || (!d_out && out_bytes) || !out_off || !d_out_len || !d_status)
+    return fail(c, HBX_E_INVALID_ARG, "%s: bad args", fn);
+  const uint32_t k = c->bc_k, m = c->bc_m, n = k + m;
+  if (na > 65535) return fail(c, HBX_E_INVALID_ARG, "%s: at most 65535 attempts per call", fn);
+  if (int rc = hbx_bcplan::check_attempts(insts, roots, len, use, na, n, c->bc_inst, c->bc_max))
+    return bc_plan_rejected(c, rc, fn);
+  if (int rc = hbx_bcplan::check_out(len, out_off, na, k, out_bytes)) return bc_plan_rejected(c, rc, fn);
+  std::vector<uint64_t> off;
+  std::vector<uint32_t> pitch;
+  const uint64_t work_bytes = hbx_bcplan::work_layout(len, na, n, off, pitch);
+  uint32_t max_len = 0;
+  for (uint32_t a = 0; a < na; a++) max_len = std::max(max_len, len[a]);
+  HBX_ENTER(c, stream);
+  int rc = rs_setup(c, k, m, s);
+  if (rc) return rc;
+  const size_t cells = (size_t)na * n;
+  if (!c->bc_work.ensure(work_bytes) || !c->bc_present.ensure(cells) || !c->bc_leaf_w.ensure(cells * 32) ||
+      !c->bc_size_bad.ensure((size_t)na * 4) || !c->roots.ensure((size_t)na * 32) || !c->leaf_hash.ensure(cells * 32) ||
+      !c->leaf_slots.ensure((size_t)na * (m ? m : 1) * 2))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "%s: out of device memory", fn);
+  // staging: rg_desc[na] | out_off u64[na] | insts u32[na] | roots [na][32] | use [na][n]
+  const size_t o_out = (size_t)na * sizeof(rg_desc), o_inst = o_out + (size_t)na * 8, o_root = o_inst + (size_t)na * 4,
+               o_use = o_root + (size_t)na * 32, bytes = o_use + cells;
+  uint8_t* h = staging_begin(c, bytes);
+  if (!h) return fail(c, HBX_E_OUT_OF_MEMORY, "%s: descriptor staging", fn);
+  rg_fill(reinterpret_cast<rg_desc*>(h), off.data(), len, pitch.data(), na);
+  memcpy(h + o_out, out_off, (size_t)na * 8);
+  memcpy(h + o_inst, insts, (size_t)na * 4);
+  memcpy(h + o_root, roots, (size_t)na * 32);
+  if (use) memcpy(h + o_use, use, cells);
+  else memset(h + o_use, 1, cells);
+  rc = staging_upload(c, bytes, s);
+  if (rc) return rc;
+  const uint8_t* dv = c->rg_dev.as<uint8_t>();
+  const rg_desc* d_desc = c->rg_dev.as<rg_desc>();
+  uint8_t* work = c->bc_work.as<uint8_t>();
+  const uint8_t* d_present = c->bc_present.as<uint8_t>();
+  HIPCHK(c, hipMemsetAsync(c->bc_size_bad.p, 0, (size_t)na * 4, s));
+  const uint32_t per_block = 256 * ECHO_COPY;
+  hipLaunchKernelGGL(k_echo_gather, dim3((max_len + per_block - 1) / per_block, n, na), dim3(256), 0, s,
+                     reinterpret_cast<const uint32_t*>(dv + o_inst), dv + o_root, dv + o_use, d_desc, n, c->bc_pitch,
+                     c->bc_shard.as<uint8_t>(), c->bc_len.as<uint32_t>(), c->bc_root.as<uint8_t>(),
+                     c->bc_leaf.as<uint8_t>(), c->bc_state.as<uint8_t>(), work, c->bc_present.as<uint8_t>(),
+                     c->bc_leaf_w.as<uint8_t>(), c->bc_size_bad.as<uint32_t>());
+  HIPCHK(c, hipGetLastError());
+  // from here on: the ragged decode's own pipeline, on the work buffer
+  rc = rs_reconstruct_rg(c, work, d_desc, max_len, d_present, na, k, m, d_status, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_echo_size_status, dim3((na + 63) / 64), dim3(64), 0, s, c->bc_size_bad.as<uint32_t>(), na,
+                     (int32_t)HBX_E_SHARD_SIZE, d_status);
+  hipLaunchKernelGGL(k_import_leaf_hashes, dim3(((uint32_t)cells * 8 + 255) / 256), dim3(256), 0, s,
+                     c->bc_leaf_w.as<uint8_t>(), d_present, (uint32_t)cells, c->leaf_hash.as<uint32_t>());
+  if (m)
+    hipLaunchKernelGGL(k_missing_slots, dim3(na), dim3(64), 0, s, d_present, n, d_status, m, c->leaf_slots.as<uint16_t>());
+  HIPCHK(c, hipGetLastError());
+  rc = merkle_tree_rg(c, work, d_desc, na, n, c->leaf_slots.as<uint16_t>(), m, m != 0, c->roots.as<uint8_t>(), nullptr, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_root_check, dim3((na + 63) / 64), dim3(64), 0, s, c->roots.as<uint8_t>(), dv + o_root, na, d_status);
+  const uint64_t glue_blocks = ((uint64_t)k * max_len + 4095) / 4096;
+  hipLaunchKernelGGL(k_glue_rg, dim3((unsigned)glue_blocks, na), dim3(256), 0, s, work, d_desc, k, d_out,
+                     reinterpret_cast<const uint64_t*>(dv + o_out), d_out_len, d_status);
+  HIPCHK(c, hipGetLastError());
+  return HBX_OK;
+}
+
+int hbx_broadcast_decode_insts(hbx_ctx* c, const uint32_t* insts, const uint8_t* roots, const uint32_t* len,
+                               const uint8_t* use, uint32_t na, uint8_t* out, uint64_t out_bytes, const uint64_t* out_off,
+                               uint64_t* out_len, int32_t* status) {
+  const char* fn = "hbx_broadcast_decode_insts";
+  if (!c) return HBX_E_INVALID_ARG;
+  if (!c->bc_live) return fail(c, HBX_E_NO_BROADCAST, "%s: no echo store (hbx_prepare_broadcast)", fn);
+  if (na == 0) return HBX_OK;
+  if ((!out && out_bytes) || !out_len || !status) return fail(c, HBX_E_INVALID_ARG, "%s: bad args", fn);
+  HBX_ENTER(c, c->stream);
+  HBX_STAGE(dout, 0, out_bytes, fn);
+  HBX_STAGE(dlen, 1, (size_t)na * 12, fn);  // out_len (u64) | status (i32)
+  HIPCHK(c, hipMemsetAsync(dout, 0, out_bytes ? out_bytes : 1, c->stream));  // bytes past a payload: 0
+  if (int rc = hbx_broadcast_decode_insts_d(c, insts, roots, len, use, na, dout, out_bytes, out_off, (uint64_t*)dlen,
+                                            (int32_t*)(dlen + (size_t)na * 8), c->stream))
+    return rc;
+  if (out_bytes) HBX_D2H(out, dout, out_bytes);
+  HBX_D2H(out_len, dlen, (size_t)na * 8);
+  HBX_D2H(status, dlen + (size_t)na * 8, (size_t)na * 4);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return HBX_OK;
+}
+
+int hbx_get_echo_slots(hbx_ctx* c, uint8_t* state, uint32_t* len, uint8_t* root) {
+  const char* fn = "hbx_get_echo_slots";
+  if (!c) return HBX_E_INVALID_ARG;
+  if (!c->bc_live) return fail(c, HBX_E_NO_BROADCAST, "%s: no echo store (hbx_prepare_broadcast)", fn);
+  HBX_ENTER(c, c->stream);
+  const size_t slots = (size_t)c->bc_inst * (c->bc_k + c->bc_m);
+  if (state) HBX_D2H(state, c->bc_state.p, slots);
+  if (len) HBX_D2H(len, c->bc_len.p, slots * 4);
+  if (root) HBX_D2H(root, c->bc_root.p, slots * 32);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return HBX_OK;
+}
+
+int hbx_debug_get_echo_rows(hbx_ctx* c, uint8_t* rows, uint64_t bytes) {
+  const char* fn = "hbx_debug_get_echo_rows";
+  if (!c || !rows) return fail(c, HBX_E_INVALID_ARG, "%s: bad args", fn);
+  if (!c->bc_live) return fail(c, HBX_E_NO_BROADCAST, "%s: no echo store (hbx_prepare_broadcast)", fn);
+  const uint64_t have = ((uint64_t)c->bc_inst * (c->bc_k + c->bc_m) + 1) * c->bc_pitch;
+  if (bytes > have) return fail(c, HBX_E_INVALID_ARG, "%s: the store's rows are %llu bytes", fn, (unsigned long long)have);
+  HBX_ENTER(c, c->stream);
+  if (bytes) HBX_D2H(rows, c->bc_shard.p, bytes);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return HBX_OK;
 }
 #undef HBX_STAGE
 #undef HBX_H2D

@@ -28,6 +28,8 @@ HBX_E_OUT_OF_MEMORY = -8
 HBX_E_TOO_FEW_SHARDS = -9
 HBX_E_ROOT_MISMATCH = -10
 HBX_E_NO_PAYLOAD = -11
+HBX_E_NO_BROADCAST = -12
+HBX_E_SHARD_SIZE = -13
 
 # Every symbol include/hbx.h declares (checked by tests/test_abi.py).
 EXPORTS = (
@@ -121,6 +123,13 @@ EXPORTS = (
     "hbx_combine_signatures_insts_d",
     "hbx_combine_signatures_insts",
     "hbx_get_coin_tiles_used",
+    "hbx_prepare_broadcast",
+    "hbx_add_echoes_d",
+    "hbx_add_echoes",
+    "hbx_broadcast_decode_insts_d",
+    "hbx_broadcast_decode_insts",
+    "hbx_get_echo_slots",
+    "hbx_debug_get_echo_rows",
 )
 
 DIGEST_SHA256 = 0
@@ -135,6 +144,11 @@ SHARE_ABSENT = 2
 SHARE_UNDECODABLE = 3
 SHARE_SKIPPED_CT = 4
 SHARE_UNKNOWN_SENDER = 5
+# hbx_add_echoes[_d] item statuses (include/hbx.h HBX_ECHO_*)
+ECHO_INVALID = 0
+ECHO_STORED = 1
+ECHO_DUPLICATE = 2
+ECHO_OVERSIZE = 3
 CT_INVALID = 0
 CT_VALID = 1
 CT_UNDECODABLE = 3
@@ -307,6 +321,16 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.hbx_combine_signatures_insts.argtypes = [P, u8p, u32, u32p, u32, u8p, u8p, i32p, u8p, u8p]
         lib.hbx_get_coin_tiles_used.argtypes = [P]
         lib.hbx_get_coin_tiles_used.restype = u32
+    # Broadcast message by message (the echo store): absent from a library built before it
+    if hasattr(lib, "hbx_prepare_broadcast"):
+        u64 = ctypes.c_uint64
+        lib.hbx_prepare_broadcast.argtypes = [P, u32, u32, u32, u32]
+        lib.hbx_add_echoes_d.argtypes = [P, P, u64, P, P, P, P, P, P, P, P, u32, P, P]
+        lib.hbx_add_echoes.argtypes = [P, P, u64, P, P, P, P, P, P, P, P, u32, P]
+        lib.hbx_broadcast_decode_insts_d.argtypes = [P, P, P, P, P, u32, P, u64, P, P, P, P]
+        lib.hbx_broadcast_decode_insts.argtypes = [P, P, P, P, P, u32, P, u64, P, P, P]
+        lib.hbx_get_echo_slots.argtypes = [P, P, P, P]
+        lib.hbx_debug_get_echo_rows.argtypes = [P, P, u64]
     # the live-allocation count: absent from a library built before it
     if hasattr(lib, "hbx_debug_live_buffers"):
         lib.hbx_debug_live_buffers.argtypes = []
@@ -1340,6 +1364,176 @@ class Context:
             self.h, d_buf.data_ptr(), nb, off.ctypes.data, lens.ctypes.data, pitch.ctypes.data, d_present.data_ptr(),
             None if d_leaf_hash is None else d_leaf_hash.data_ptr(), d_root.data_ptr(), inst, k, m, d_out.data_ptr(), ob,
             out_off.ctypes.data, d_out_len.data_ptr(), d_status.data_ptr(), self._stream(stream)))
+
+    # -- Broadcast, message by message: the echo store, adds and listed decodes ---------------------
+    def prepare_broadcast(self, inst: int, k: int, m: int, max_shard_len: int):
+        """hbx_prepare_broadcast: an empty echo store of inst x (k + m) slots of max_shard_len bytes."""
+        for name, v in (("inst", inst), ("k", k), ("max_shard_len", max_shard_len)):
+            if not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f"prepare_broadcast: {name} must be a positive integer")
+        if not isinstance(m, (int, np.integer)) or m < 0 or k > 128 or k + m > 256:
+            raise ValueError("prepare_broadcast: need 1 <= k <= 128, m >= 0 and k + m <= 256")
+        if max_shard_len > 0xFFFFFFF0:
+            raise ValueError("prepare_broadcast: max_shard_len does not fit the store's rows")
+        self._check(self.lib.hbx_prepare_broadcast(self.h, int(inst), int(k), int(m), int(max_shard_len)))
+        self._bc = (int(inst), int(k) + int(m), int(k), (int(max_shard_len) + 3) // 4 * 4)
+
+    @staticmethod
+    def _echo_items(what: str, val_off, inst, sender, nbytes: int):
+        """The host arrays of an add: val_off uint64[count + 1] within nbytes, (inst, sender) pairs
+        each once."""
+        val_off = np.asarray(val_off)
+        if val_off.ndim != 1 or val_off.size < 1 or val_off.dtype.kind not in "iu" or (val_off.size and int(val_off.min()) < 0):
+            raise ValueError(f"{what}: val_off must be count + 1 offsets")
+        count = val_off.size - 1
+        val_off = np.ascontiguousarray(val_off, dtype=np.uint64)
+        if (val_off[1:] < val_off[:-1]).any() or int(val_off[-1]) > nbytes:
+            raise ValueError(f"{what}: val_off must be non-decreasing and end within the values ({nbytes} bytes)")
+        inst, sender = Context._index_pair(what, ("inst", "sender"), inst, sender, count)
+        pairs = set(zip(inst.tolist(), sender.tolist()))
+        if len(pairs) != count:
+            raise ValueError(f"{what}: the same (inst, sender) twice in one call")
+        return val_off, inst, sender, count
+
+    def add_echoes(self, values, val_off, nodes, sibs, sides, depth, root, inst, sender) -> np.ndarray:
+        """hbx_add_echoes: host arrays in the layout of flatten_proofs_ragged (values uint8[bytes],
+        val_off [count + 1], nodes uint8[count, 17, 32], sibs uint8[count, 16, 32], sides / depth
+        uint32[count], root uint8[count, 32]) and the items' (inst, sender) -> HBX_ECHO_* uint8[count]."""
+        what = "add_echoes"
+        values = np.asarray(values)
+        if values.dtype != np.uint8 or values.ndim != 1:
+            raise ValueError(f"{what}: values must be uint8[bytes], not {values.dtype}{values.shape}")
+        values = np.ascontiguousarray(values)
+        val_off, inst, sender, count = self._echo_items(what, val_off, inst, sender, values.size)
+
+        def arr(name, a, dtype, shape):
+            a = np.asarray(a)
+            if a.dtype != dtype or a.shape != shape:
+                raise ValueError(f"{what}: {name} must be {np.dtype(dtype)}{list(shape)}, not {a.dtype}{list(a.shape)}")
+            return np.ascontiguousarray(a)
+
+        nodes = arr("nodes", nodes, np.uint8, (count, 17, 32))
+        sibs = arr("sibs", sibs, np.uint8, (count, 16, 32))
+        sides = arr("sides", sides, np.uint32, (count,))
+        depth = arr("depth", depth, np.uint32, (count,))
+        root = arr("root", root, np.uint8, (count, 32))
+        out = np.zeros(count, dtype=np.uint8)
+        if count:
+            keep = values if values.size else np.zeros(1, dtype=np.uint8)
+            self._check(self.lib.hbx_add_echoes(
+                self.h, keep.ctypes.data, values.size, val_off.ctypes.data, nodes.ctypes.data, sibs.ctypes.data,
+                sides.ctypes.data, depth.ctypes.data, root.ctypes.data, inst.ctypes.data, sender.ctypes.data, count,
+                out.ctypes.data))
+        return out
+
+    def add_echoes_d(self, d_values, val_off, d_nodes, d_sibs, d_sides, d_depth, d_root, inst, sender, d_status=None,
+                     stream=None):
+        """hbx_add_echoes_d: the device tensors of merkle_validate_ragged_d, host val_off / inst /
+        sender, d_status an optional device uint8[count]."""
+        what = "add_echoes_d"
+        nb = self._flat_u8(what, d_values)
+        val_off, inst, sender, count = self._echo_items(what, val_off, inst, sender, nb)
+        for name, t, cells, width in (("d_nodes", d_nodes, count * 17 * 32, 1), ("d_sibs", d_sibs, count * 16 * 32, 1),
+                                      ("d_sides", d_sides, count, 4), ("d_depth", d_depth, count, 4),
+                                      ("d_root", d_root, count * 32, 1)):
+            if t.numel() != cells or t.element_size() != width or not t.is_contiguous():
+                raise ValueError(f"{what}: {name} must be contiguous with {cells} elements of {width} byte(s)")
+        if d_status is not None and (d_status.numel() != count or d_status.element_size() != 1):
+            raise ValueError(f"{what}: d_status must have one byte per item ({count})")
+        if count:
+            self._check(self.lib.hbx_add_echoes_d(
+                self.h, d_values.data_ptr(), nb, val_off.ctypes.data, d_nodes.data_ptr(), d_sibs.data_ptr(),
+                d_sides.data_ptr(), d_depth.data_ptr(), d_root.data_ptr(), inst.ctypes.data, sender.ctypes.data, count,
+                None if d_status is None else d_status.data_ptr(), self._stream(stream)))
+
+    @staticmethod
+    def _attempts(what: str, insts, roots, lens, use, n):
+        """A decode list: insts uint32[na], roots uint8[na, 32], lens uint32[na] >= 1, use None or
+        uint8[na, n]; each (instance, root, use row) once."""
+        insts = np.asarray(insts)
+        if insts.ndim != 1 or (insts.size and (insts.dtype.kind not in "iu" or int(insts.min()) < 0)):
+            raise ValueError(f"{what}: insts must be a list of instances")
+        na = insts.size
+        insts = np.ascontiguousarray(insts, dtype=np.uint32)
+        roots = np.asarray(roots)
+        if roots.dtype != np.uint8 or roots.shape != (na, 32):
+            raise ValueError(f"{what}: roots must be uint8[{na}, 32], not {roots.dtype}{roots.shape}")
+        roots = np.ascontiguousarray(roots)
+        lens = np.asarray(lens)
+        if lens.shape != (na,) or (na and (lens.dtype.kind not in "iu" or int(lens.min()) < 1 or int(lens.max()) > 0xFFFFFFFF)):
+            raise ValueError(f"{what}: len must hold one shard length >= 1 per attempt")
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        if use is not None:
+            use = np.asarray(use)
+            if n is None or use.dtype not in (np.uint8, np.bool_) or use.shape != (na, n):
+                raise ValueError(f"{what}: use must be uint8[{na}, n = {n}], not {use.dtype}{use.shape}")
+            use = np.ascontiguousarray(use != 0, dtype=np.uint8)  # a byte allows its sender iff non-zero
+        keys = {(int(insts[a]), roots[a].tobytes(), None if use is None else use[a].tobytes()) for a in range(na)}
+        if len(keys) != na:
+            raise ValueError(f"{what}: the same (instance, root, use row) is listed twice")
+        return insts, roots, lens, use, na
+
+    def _bc_dims(self, what: str):
+        bc = getattr(self, "_bc", None)
+        if bc is None:
+            raise ValueError(f"{what}: no echo store (prepare_broadcast)")
+        return bc
+
+    def broadcast_decode_insts(self, insts, roots, lens, use=None, n=None):
+        """hbx_broadcast_decode_insts: the listed attempts out of the echo store -> (payloads
+        [bytes | None per attempt], status int32[na]).  n: the node count `use` rows must have
+        (default: the prepared store's)."""
+        what = "broadcast_decode_insts"
+        if n is None:
+            n = self._bc_dims(what)[1]
+        insts, roots, lens, use, na = self._attempts(what, insts, roots, lens, use, n)
+        if na == 0:
+            return [], np.zeros(0, dtype=np.int32)
+        k = self._bc_dims(what)[2]
+        room = (np.maximum(k * lens.astype(np.int64) - 4, 0) + 15) // 16 * 16
+        out_off = np.concatenate(([0], np.cumsum(room)[:-1])).astype(np.uint64)
+        out = np.zeros(max(int(room.sum()), 16), dtype=np.uint8)
+        out_len = np.zeros(na, dtype=np.uint64)
+        status = np.zeros(na, dtype=np.int32)
+        self._check(self.lib.hbx_broadcast_decode_insts(
+            self.h, insts.ctypes.data, roots.ctypes.data, lens.ctypes.data, None if use is None else use.ctypes.data, na,
+            out.ctypes.data, out.size, out_off.ctypes.data, out_len.ctypes.data, status.ctypes.data))
+        vals = [out[int(o): int(o) + int(ln)].tobytes() if st == 0 else None for o, ln, st in zip(out_off, out_len, status)]
+        return vals, status
+
+    def broadcast_decode_insts_d(self, insts, roots, lens, d_out, out_off, d_out_len, d_status, use=None, n=None,
+                                 stream=None):
+        """hbx_broadcast_decode_insts_d: host insts / roots / lens / use / out_off; attempt a's payload at
+        d_out[out_off[a]:], d_out_len int64[na], d_status int32[na]."""
+        what = "broadcast_decode_insts_d"
+        if n is None:
+            n = self._bc_dims(what)[1]
+        insts, roots, lens, use, na = self._attempts(what, insts, roots, lens, use, n)
+        ob = self._flat_u8(what, d_out)
+        out_off = np.ascontiguousarray(out_off, dtype=np.uint64).reshape(-1)
+        if out_off.size != na or d_out_len.numel() != na or d_status.numel() != na or d_out_len.element_size() != 8 \
+                or d_status.element_size() != 4:
+            raise ValueError(f"{what}: out_off, d_out_len (64-bit) and d_status (32-bit) need {na} entries")
+        if na:
+            self._check(self.lib.hbx_broadcast_decode_insts_d(
+                self.h, insts.ctypes.data, roots.ctypes.data, lens.ctypes.data, None if use is None else use.ctypes.data,
+                na, d_out.data_ptr(), ob, out_off.ctypes.data, d_out_len.data_ptr(), d_status.data_ptr(),
+                self._stream(stream)))
+
+    def echo_slots(self, rows: bool = False):
+        """hbx_get_echo_slots: (state uint8[inst, n], len uint32[inst, n], root uint8[inst, n, 32]) of
+        the echo store; rows=True adds the shard rows uint8[inst * n + 1, pitch] (hbx_debug_get_echo_rows:
+        the last one is the canary row)."""
+        inst, n, _, pitch = self._bc_dims("echo_slots")
+        state = np.zeros((inst, n), dtype=np.uint8)
+        lens = np.zeros((inst, n), dtype=np.uint32)
+        root = np.zeros((inst, n, 32), dtype=np.uint8)
+        self._check(self.lib.hbx_get_echo_slots(self.h, state.ctypes.data, lens.ctypes.data, root.ctypes.data))
+        if not rows:
+            return state, lens, root
+        buf = np.zeros((inst * n + 1, pitch), dtype=np.uint8)
+        self._check(self.lib.hbx_debug_get_echo_rows(self.h, buf.ctypes.data, buf.size))
+        return state, lens, root, buf
 
     def get_ct_valid_d(self, d_ct_valid, stream=None):
         self._check(self.lib.hbx_get_ct_valid_d(self.h, d_ct_valid.data_ptr(), self._stream(stream)))

@@ -44,6 +44,8 @@ extern "C" {
 #define HBX_E_TOO_FEW_SHARDS (-9)    /* reed_solomon_erasure Error::TooFewShardsPresent */
 #define HBX_E_ROOT_MISMATCH (-10)    /* decode_from_shards: rebuilt Merkle root != hash (broadcast.rs:686) */
 #define HBX_E_NO_PAYLOAD (-11)       /* glue_shards: fewer than 4 bytes (broadcast.rs:702) */
+#define HBX_E_NO_BROADCAST (-12)     /* hbx_prepare_broadcast not called, or its store voided */
+#define HBX_E_SHARD_SIZE (-13)       /* reed_solomon_erasure Error::IncorrectShardSize */
 
 /* per-point decode status (hbx_set_pk_shares / hbx_prepare_ciphertexts) */
 #define HBX_PT_OK 0
@@ -751,6 +753,84 @@ int hbx_broadcast_decode_ragged_d(hbx_ctx* ctx, uint8_t* d_buf, uint64_t buf_byt
                                   const uint8_t* d_leaf_hash, const uint8_t* d_root_expect, uint32_t inst,
                                   uint32_t k, uint32_t m, uint8_t* d_out, uint64_t out_bytes,
                                   const uint64_t* out_off, uint64_t* d_out_len, int32_t* d_status, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Broadcast, message by message: the node that is running an epoch.  Echoes arrive a few at a
+ * time; each is validated once, on arrival, and its value stays on the device until its
+ * instance's compute_output decodes it (src/broadcast.rs:521-551).
+ *
+ * hbx_prepare_broadcast -- the echo store of `inst` instances x n = k + m senders (k + m <= 256,
+ *   k <= 128).  Slot (q, i) holds the first validated Echo value of sender i in instance q: a state
+ *   byte (0 empty, 1 held), the shard length and bytes (the value without its index byte; rows of
+ *   max_shard_len rounded up to 4), the proof's root and its leaf digest (the last lemma node).  A
+ *   value longer than max_shard_len + 1 bytes cannot be held (HBX_ECHO_OVERSIZE): max_shard_len is
+ *   the caller's transport bound, the store does not grow.  A second prepare with the same
+ *   dimensions only empties the slots.  hbx_set_merkle_digest voids the store (its values were
+ *   validated under the other digest); the calls below return HBX_E_NO_BROADCAST on a voided or
+ *   never prepared store.
+ *
+ * hbx_add_echoes[_d] -- Broadcast::handle_echo up to echos.insert (src/broadcast.rs:439-458), and
+ *   handle_value -> send_echo -> handle_echo(our_uid) (:407-436, :494-504): a Value from the
+ *   proposer is an item with sender = this node.  Item j is value
+ *   d_values[val_off[j] .. val_off[j + 1]) (val_off: HOST, count + 1 entries) with the flattened
+ *   proof j of hbx_merkle_validate_ragged_d, for slot (inst[j], sender[j]) (HOST arrays, consumed at
+ *   return).  d_status[count] (may be NULL), one HBX_ECHO_* byte per item:
+ *     HBX_ECHO_DUPLICATE  the slot is already held; the bytes are not looked at (:441-448);
+ *     HBX_ECHO_OVERSIZE   the value is longer than max_shard_len + 1; not validated, not stored;
+ *     HBX_ECHO_INVALID    validate_proof(p, sender) is false -- the bit hbx_merkle_validate_ragged_d
+ *                         writes for the same proof and sender (an empty value is invalid); the slot
+ *                         stays empty, so a later Echo of that sender is still looked at;
+ *     HBX_ECHO_STORED     valid and the slot was empty: it takes length, bytes, root, leaf digest.
+ *   No other slot changes, so any partition of an epoch's Echoes into calls that keeps each (inst,
+ *   sender) pair's own order leaves the same store.  HBX_E_INVALID_ARG before anything is launched,
+ *   nothing changed: inst[j] >= the store's instance count; sender[j] >= n; the same (inst, sender)
+ *   twice in one call (repeats go into later calls); val_off decreasing or ending past
+ *   values_bytes.  count == 0 does nothing.  The _d form is stream-ordered and does not
+ *   synchronise; the host form blocks.
+ *
+ * hbx_broadcast_decode_insts[_d] -- compute_output's decode_from_shards + glue_shards
+ *   (src/broadcast.rs:530-551, :660-707) for the listed attempts only.  Attempt a = instance
+ *   insts[a], root roots[a][32], shard length len[a] (>= 1, <= max_shard_len) and, optionally,
+ *   use[a][n] bytes: the Echo senders held when the trigger fired (NULL: all).  insts, roots, len,
+ *   use and out_off are HOST arrays, consumed at return.  Shard i is present iff use allows it, slot
+ *   (insts[a], i) is held and its root is roots[a].  d_status[a]: HBX_E_SHARD_SIZE if a present
+ *   slot's length is not len[a] (decode_from_shards returns None: the crate checks shard sizes
+ *   before it counts shards, so this code wins over HBX_E_TOO_FEW_SHARDS when both apply); every
+ *   other status, d_out / out_off / d_out_len as hbx_broadcast_decode_ragged_d.  The store is never
+ *   written: the present rows are copied into a work buffer the context owns and reconstructed
+ *   there, so a failed attempt can be retried with later Echoes (:543-550) and slots holding
+ *   another root survive.  HBX_E_INVALID_ARG before any launch: an instance beyond the store's;
+ *   the same (instance, root, use row) twice; len[a] == 0 or > max_shard_len; more than 65535
+ *   attempts in one call; output room as in the ragged decode (d_out may be NULL only when
+ *   out_bytes == 0).  na == 0 returns HBX_OK.  A use byte allows its sender iff it is non-zero; two
+ *   rows that allow the same senders are the same row.
+ *
+ * hbx_get_echo_slots -- the store as the host sees it (diagnostics, tests): state[inst][n],
+ *   len[inst][n], root[inst][n][32]; any may be NULL.  hbx_debug_get_echo_rows (tests only, like
+ *   hbx_debug_live_buffers): the first `bytes` bytes of the shard rows (inst * n rows of the row
+ *   pitch, then one canary row of 0xA5 that nothing may write).
+ * ------------------------------------------------------------------------------------------- */
+#define HBX_ECHO_INVALID 0
+#define HBX_ECHO_STORED 1
+#define HBX_ECHO_DUPLICATE 2
+#define HBX_ECHO_OVERSIZE 3
+int hbx_prepare_broadcast(hbx_ctx* ctx, uint32_t inst, uint32_t k, uint32_t m, uint32_t max_shard_len);
+int hbx_add_echoes_d(hbx_ctx* ctx, const uint8_t* d_values, uint64_t values_bytes, const uint64_t* val_off,
+                     const uint8_t* d_node_hash, const uint8_t* d_sib_hash, const uint32_t* d_sides,
+                     const uint32_t* d_depth, const uint8_t* d_root, const uint32_t* inst, const uint32_t* sender,
+                     uint32_t count, uint8_t* d_status, void* stream);
+int hbx_add_echoes(hbx_ctx* ctx, const uint8_t* values, uint64_t values_bytes, const uint64_t* val_off,
+                   const uint8_t* node_hash, const uint8_t* sib_hash, const uint32_t* sides, const uint32_t* depth,
+                   const uint8_t* root, const uint32_t* inst, const uint32_t* sender, uint32_t count,
+                   uint8_t* status);
+int hbx_broadcast_decode_insts_d(hbx_ctx* ctx, const uint32_t* insts, const uint8_t* roots, const uint32_t* len,
+                                 const uint8_t* use, uint32_t na, uint8_t* d_out, uint64_t out_bytes,
+                                 const uint64_t* out_off, uint64_t* d_out_len, int32_t* d_status, void* stream);
+int hbx_broadcast_decode_insts(hbx_ctx* ctx, const uint32_t* insts, const uint8_t* roots, const uint32_t* len,
+                               const uint8_t* use, uint32_t na, uint8_t* out, uint64_t out_bytes,
+                               const uint64_t* out_off, uint64_t* out_len, int32_t* status);
+int hbx_get_echo_slots(hbx_ctx* ctx, uint8_t* state, uint32_t* len, uint8_t* root);
+int hbx_debug_get_echo_rows(hbx_ctx* ctx, uint8_t* rows, uint64_t bytes);
 
 /* Host-pointer forms of the Broadcast calls: the same operations and layouts on HOST buffers,
  * staged through device buffers the context owns, on the context's own stream; they block until
