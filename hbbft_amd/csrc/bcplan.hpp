@@ -1,6 +1,6 @@
-// Host planning of the echo store's two calls (include/hbx.h: hbx_add_echoes_d,
-// hbx_broadcast_decode_insts_d): the argument checks that come before any launch, the grouping of an
-// add's long values by length into hash blocks, and the work-buffer layout of a decode list.
+// Host planning of the Broadcast calls that take host lists (include/hbx.h: the *_ragged_d forms,
+// hbx_add_echoes_d, hbx_broadcast_decode_insts_d): the argument checks that come before any launch,
+// the grouping of long values by length into hash blocks, and the work-buffer layout of a decode list.
 // Host-only and free of HIP, so tools/hostcheck/bcplancheck.cpp builds it with a plain C++ compiler
 // (tests/test_bcplan.py).
 #pragma once
@@ -40,10 +40,12 @@ inline int check_items(const uint32_t* inst, const uint32_t* sender, uint32_t co
   return std::adjacent_find(keys.begin(), keys.end()) != keys.end() ? PLAN_DUPLICATE : PLAN_OK;
 }
 
-inline int check_offsets(const uint64_t* val_off, uint32_t count, uint64_t values_bytes) {
-  for (uint32_t j = 0; j < count; j++)
-    if (val_off[j + 1] < val_off[j] || val_off[j + 1] - val_off[j] > 0xFFFFFFFFull) return PLAN_BAD_OFFSETS;
-  return val_off[count] > values_bytes ? PLAN_BAD_OFFSETS : PLAN_OK;
+// *bad (optional) = the first j whose val_off[j..j + 1] is no value; `count`: the list ends past the blob.
+inline int check_offsets(const uint64_t* val_off, uint32_t count, uint64_t values_bytes, uint32_t* bad = nullptr) {
+  uint32_t j = 0;
+  while (j < count && val_off[j + 1] >= val_off[j] && val_off[j + 1] - val_off[j] <= 0xFFFFFFFFull) j++;
+  if (bad) *bad = j;
+  return j < count || val_off[count] > values_bytes ? PLAN_BAD_OFFSETS : PLAN_OK;
 }
 
 // The values longer than IN_LANE_MAX bytes (and, with max_value != 0, no longer than it: an
@@ -111,18 +113,47 @@ inline uint64_t work_layout(const uint32_t* len, uint32_t na, uint32_t n, std::v
 }
 
 // Output room as in the ragged decode: attempt a may write k len[a] - 4 bytes at out_off[a], apart
-// from the others' ranges.
-inline int check_out(const uint32_t* len, const uint64_t* out_off, uint32_t na, uint32_t k, uint64_t out_bytes) {
+// from the others' ranges.  *bad (optional) = the first attempt without room; `na`: ranges overlap.
+inline int check_out(const uint32_t* len, const uint64_t* out_off, uint32_t na, uint32_t k, uint64_t out_bytes,
+                     uint32_t* bad = nullptr) {
   std::vector<std::pair<uint64_t, uint64_t>> rng;
   for (uint32_t a = 0; a < na; a++) {
     const uint64_t need = (uint64_t)k * len[a] >= 4 ? (uint64_t)k * len[a] - 4 : 0;
+    if (bad) *bad = a;
     if (out_off[a] > out_bytes || need > out_bytes - out_off[a]) return PLAN_NO_ROOM;
     if (need) rng.emplace_back(out_off[a], out_off[a] + need);
   }
+  if (bad) *bad = na;
   std::sort(rng.begin(), rng.end());
   for (size_t r = 1; r < rng.size(); r++)
     if (rng[r].first < rng[r - 1].second) return PLAN_NO_ROOM;
   return PLAN_OK;
+}
+
+enum { ROWS_OK = 0, ROWS_UNALIGNED = 1, ROWS_BAD_LEN = 2, ROWS_PAST_END = 3, ROWS_OVERLAP = 4 };
+
+// The row descriptors of a ragged call (include/hbx.h; instance q's n rows of len[q] bytes start at
+// off[q], pitch[q] apart), per instance in turn, then no two instances' rows overlap.  bad[0] (and
+// bad[1] of an overlapping pair, in offset order) = the offending instance; *max_len = the longest shard.
+inline int check_rows(uint64_t buf_bytes, const uint64_t* off, const uint32_t* len, const uint32_t* pitch, uint32_t inst,
+                      uint32_t n, uint32_t* max_len, uint32_t bad[2]) {
+  uint32_t mx = 0;
+  for (uint32_t q = 0; q < inst; q++) {
+    bad[0] = q;
+    if (off[q] % 4 || pitch[q] % 4) return ROWS_UNALIGNED;
+    if (len[q] == 0 || pitch[q] < len[q]) return ROWS_BAD_LEN;
+    if (off[q] > buf_bytes || (uint64_t)n * pitch[q] > buf_bytes - off[q]) return ROWS_PAST_END;
+    if (len[q] > mx) mx = len[q];
+  }
+  std::vector<uint32_t> order(inst);
+  for (uint32_t q = 0; q < inst; q++) order[q] = q;
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return off[a] < off[b]; });
+  for (uint32_t r = 1; r < inst; r++) {
+    bad[0] = order[r - 1], bad[1] = order[r];
+    if (off[bad[1]] < off[bad[0]] + (uint64_t)n * pitch[bad[0]]) return ROWS_OVERLAP;
+  }
+  *max_len = mx;
+  return ROWS_OK;
 }
 
 }  // namespace hbx_bcplan

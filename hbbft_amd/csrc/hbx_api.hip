@@ -10,7 +10,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -510,6 +512,18 @@ static int rs_tile3(uint32_t k, uint32_t no) {
   return ch;
 }
 
+// Calls f with tile `ch` of rs_ch3 as a compile-time constant (std::integral_constant<int, CH>).
+template <class F>
+static void rs_with_tile(int ch, F&& f) {
+  switch (ch) {
+    case 42: return f(std::integral_constant<int, 42>{});
+    case 28: return f(std::integral_constant<int, 28>{});
+    case 14: return f(std::integral_constant<int, 14>{});
+    case 12: return f(std::integral_constant<int, 12>{});
+    default: return f(std::integral_constant<int, 21>{});
+  }
+}
+
 // One coding pass: the triple byte-permute kernel (4.0 VALU ops per coefficient-dword) when rows
 // are whole dwords, else the LDS log/exp one.
 // `no` is the outputs one instance's pass is expected to write: m on encode; on a reconstruct pass
@@ -536,18 +550,11 @@ static void rs_code(hbx_ctx* c, uint8_t* d_shards, size_t stride, uint32_t L, ui
     return 0;
   }();
   if (pin && rs_perm3_lds_bytes(k, pin) <= 65536) ch = pin;
-  switch (ch) {
-#define HBX_RS_TILE3(c3)                                                                                          \
-  hipLaunchKernelGGL((k_rs_code_perm3<c3, 2>), dim3((Ld + 511) / 512, inst, (no + c3 - 1) / c3), dim3(256),        \
-                     rs_perm3_lds_bytes(k, c3), s, d_shards, stride, L, k, jobs, ptab, job_stride);                \
-  break;
-    case 42: HBX_RS_TILE3(42)
-    case 28: HBX_RS_TILE3(28)
-    case 14: HBX_RS_TILE3(14)
-    case 12: HBX_RS_TILE3(12)
-    default: HBX_RS_TILE3(21)
-#undef HBX_RS_TILE3
-  }
+  rs_with_tile(ch, [&](auto tile) {
+    constexpr int c3 = decltype(tile)::value;
+    hipLaunchKernelGGL((k_rs_code_perm3<c3, 2>), dim3((Ld + 511) / 512, inst, (no + c3 - 1) / c3), dim3(256),
+                       rs_perm3_lds_bytes(k, c3), s, d_shards, stride, L, k, jobs, ptab, job_stride);
+  });
 }
 
 // Encoding matrix V * inverse(V[0..k]) with V[r][c] = r^c ((k + m) x k, reed-solomon-erasure 3.1.0).
@@ -584,9 +591,14 @@ static bool rs_matrix(uint32_t k, uint32_t m, std::vector<uint8_t>& out) {
   return true;
 }
 
-static int rs_setup(hbx_ctx* c, uint32_t k, uint32_t m, hipStream_t s) {
+static int rs_bounds(hbx_ctx* c, uint32_t k, uint32_t m) {
   if (k == 0 || k > (uint32_t)RS_MAX_K || k + m > (uint32_t)RS_MAX_N)
     return fail(c, HBX_E_INVALID_ARG, "rs: need 1 <= k <= %d and k + m <= %d (k=%u m=%u)", RS_MAX_K, RS_MAX_N, k, m);
+  return HBX_OK;
+}
+
+static int rs_setup(hbx_ctx* c, uint32_t k, uint32_t m, hipStream_t s) {
+  if (int rc = rs_bounds(c, k, m)) return rc;
   if (!c->gf_log.p) {
     if (!c->gf_log.ensure(512) || !c->gf_exp.ensure(768)) return fail(c, HBX_E_OUT_OF_MEMORY, "rs: tables");
     HIPCHK(c, hipMemcpyAsync(c->gf_log.p, gf().lg, 512, hipMemcpyHostToDevice, s));
@@ -622,27 +634,33 @@ static int rs_setup(hbx_ctx* c, uint32_t k, uint32_t m, hipStream_t s) {
   return HBX_OK;
 }
 
-static int rs_reconstruct(hbx_ctx* c, uint8_t* d_shards, const uint8_t* d_present, uint32_t inst, uint32_t k,
-                          uint32_t m, uint32_t L, int32_t* d_status, hipStream_t s) {
-  const size_t stride = (size_t)(k + m) * L;
+// A reconstruct's set-up: per instance the status and the jobs and coefficients of its two coding
+// passes (data, then parity); with `want_perm` their byte-permute tables, which the dword kernels read.
+static int rs_reconstruct_tables(hbx_ctx* c, const uint8_t* d_present, uint32_t inst, uint32_t k, uint32_t m,
+                                 int32_t* d_status, bool want_perm, hipStream_t s) {
+  const size_t tab = (size_t)inst * RS_MAX_N * k;
   if (!c->rs_jobs_d.ensure((size_t)inst * sizeof(rs_job)) || !c->rs_jobs_p.ensure((size_t)inst * sizeof(rs_job)) ||
-      !c->rs_coef_d.ensure((size_t)inst * RS_MAX_N * k * 2) || !c->rs_coef_p.ensure((size_t)inst * RS_MAX_N * k * 2))
+      !c->rs_coef_d.ensure(tab * 2) || !c->rs_coef_p.ensure(tab * 2) ||
+      (want_perm && (!c->rs_ptab_d.ensure(tab * sizeof(gf_ptab)) || !c->rs_ptab_p.ensure(tab * sizeof(gf_ptab)))))
     return fail(c, HBX_E_OUT_OF_MEMORY, "rs_reconstruct: out of device memory");
   hipLaunchKernelGGL(k_rs_setup_reconstruct, dim3(inst), dim3(256), 0, s, d_present, k, m, c->rs_enc.as<uint8_t>(),
                      c->gf_log.as<uint16_t>(), c->gf_exp.as<uint8_t>(), c->rs_jobs_d.as<rs_job>(),
                      c->rs_coef_d.as<uint16_t>(), c->rs_jobs_p.as<rs_job>(), c->rs_coef_p.as<uint16_t>(), d_status);
-  HIPCHK(c, hipGetLastError());
-  if (L % 4 == 0) {
-    if (!c->rs_ptab_d.ensure((size_t)inst * RS_MAX_N * k * sizeof(gf_ptab)) ||
-        !c->rs_ptab_p.ensure((size_t)inst * RS_MAX_N * k * sizeof(gf_ptab)))
-      return fail(c, HBX_E_OUT_OF_MEMORY, "rs_reconstruct: out of device memory");
+  if (want_perm) {
     const dim3 tg((RS_MAX_N * k + 255) / 256, inst);
     hipLaunchKernelGGL(k_rs_perm_tables, tg, dim3(256), 0, s, c->rs_jobs_d.as<rs_job>(), c->rs_coef_d.as<uint16_t>(), k,
                        c->gf_log.as<uint16_t>(), c->gf_exp.as<uint8_t>(), c->rs_ptab_d.as<gf_ptab>());
     hipLaunchKernelGGL(k_rs_perm_tables, tg, dim3(256), 0, s, c->rs_jobs_p.as<rs_job>(), c->rs_coef_p.as<uint16_t>(), k,
                        c->gf_log.as<uint16_t>(), c->gf_exp.as<uint8_t>(), c->rs_ptab_p.as<gf_ptab>());
-    HIPCHK(c, hipGetLastError());
   }
+  HIPCHK(c, hipGetLastError());
+  return HBX_OK;
+}
+
+static int rs_reconstruct(hbx_ctx* c, uint8_t* d_shards, const uint8_t* d_present, uint32_t inst, uint32_t k,
+                          uint32_t m, uint32_t L, int32_t* d_status, hipStream_t s) {
+  const size_t stride = (size_t)(k + m) * L;
+  if (int rc = rs_reconstruct_tables(c, d_present, inst, k, m, d_status, L % 4 == 0, s)) return rc;
   rs_code(c, d_shards, stride, L, k, inst, c->rs_jobs_d.as<rs_job>(), c->rs_coef_d.as<uint16_t>(),
           c->rs_ptab_d.as<gf_ptab>(), 1u, (m + 1) / 2, s);
   HIPCHK(c, hipGetLastError());
@@ -652,25 +670,138 @@ static int rs_reconstruct(hbx_ctx* c, uint8_t* d_shards, const uint8_t* d_presen
   return HBX_OK;
 }
 
+// The leaf digests of every family (uniform or ragged leaves, ragged or echo values; a family's two
+// kernels share a signature): a SHA-256 block hashes 64 items with 128 threads, a SHA3 block 32 with
+// 64.  leaf_blocks: `blocks` of items grouped beforehand; leaf_digests: `items` in a row, `gy` times.
+static uint32_t leaf_lanes(const hbx_ctx* c) { return c->merkle == HBX_MERKLE_SHA256 ? 64 : 32; }
+
+template <class K, class... A>
+static void leaf_blocks(hbx_ctx* c, hipStream_t s, K sha256, K sha3, dim3 blocks, A... args) {
+  timed t_(c, HBX_K_MERKLE_LEAVES, s);
+  if (c->merkle == HBX_MERKLE_SHA256) hipLaunchKernelGGL(sha256, blocks, dim3(128), 0, s, args...);
+  else hipLaunchKernelGGL(sha3, blocks, dim3(64), 0, s, args...);
+}
+
+template <class K, class... A>
+static void leaf_digests(hbx_ctx* c, hipStream_t s, K sha256, K sha3, uint32_t items, uint32_t gy, A... args) {
+  leaf_blocks(c, s, sha256, sha3, dim3((items + leaf_lanes(c) - 1) / leaf_lanes(c), gy), args...);
+}
+
+// Uniform rows' leaf digests into c->leaf_hash: all n leaves, or the `nslots` listed per instance.
+static void leaves_uniform(hbx_ctx* c, hipStream_t s, const uint8_t* d_shards, uint32_t inst, uint32_t n, uint32_t L,
+                           const uint16_t* slots, uint32_t nslots) {
+  leaf_digests(c, s, k_merkle_leaves_sha256, k_merkle_leaves_sha3, slots ? nslots : n, inst, d_shards, (size_t)n * L, n,
+               L, c->leaf_hash.as<uint32_t>(), slots, nslots, 0u);
+}
+
 static int merkle_roots(hbx_ctx* c, const uint8_t* d_shards, uint32_t inst, uint32_t n, uint32_t L, uint8_t* d_roots,
                         hipStream_t s, uint8_t* d_nodes = nullptr) {
   if (n == 0 || n > (uint32_t)RS_MAX_N) return fail(c, HBX_E_INVALID_ARG, "merkle: need 1 <= n <= 256");
   if (!c->leaf_hash.ensure((size_t)inst * n * 32)) return fail(c, HBX_E_OUT_OF_MEMORY, "merkle: leaf hashes");
-  {
-    timed t_(c, HBX_K_MERKLE_LEAVES, s);
-    if (c->merkle == HBX_MERKLE_SHA256)
-      hipLaunchKernelGGL(k_merkle_leaves_sha256, dim3((n + 63) / 64, inst), dim3(128), 0, s, d_shards, (size_t)n * L,
-                         n, L, c->leaf_hash.as<uint32_t>(), (const uint16_t*)nullptr, 0u, 0u);
-    else
-      hipLaunchKernelGGL(k_merkle_leaves_sha3, dim3((n + 31) / 32, inst), dim3(64), 0, s, d_shards, (size_t)n * L, n,
-                         L, c->leaf_hash.as<uint32_t>(), (const uint16_t*)nullptr, 0u, 0u);
-  }
+  leaves_uniform(c, s, d_shards, inst, n, L, nullptr, 0);
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(k_merkle_tree, dim3(inst), dim3(128), 0, s, c->leaf_hash.as<uint32_t>(), n, d_roots, d_nodes,
                      c->merkle);
   HIPCHK(c, hipGetLastError());
   return HBX_OK;
 }
+
+// A decode after its reconstruct: the rows' trees, the roots against the expected ones into the
+// status, the glue.  With d_leaf_hash the present shards' leaf digests are taken from it (validated
+// Echo proofs) and only the reconstructed shards are hashed.  The row layout's two launches are the
+// caller's: leaves(slots, nslots) = all leaves' digests (slots == nullptr) or the listed ones', glue().
+template <class Leaves, class Glue>
+static int decode_tail(hbx_ctx* c, const uint8_t* d_present, const uint8_t* d_leaf_hash, const uint8_t* d_root_expect,
+                       uint32_t inst, uint32_t n, uint32_t m, int32_t* d_status, hipStream_t s, Leaves leaves,
+                       Glue glue) {
+  if (!c->roots.ensure((size_t)inst * 32)) return fail(c, HBX_E_OUT_OF_MEMORY, "decode: roots");
+  if (!c->leaf_hash.ensure((size_t)inst * n * 32) ||
+      (d_leaf_hash && !c->leaf_slots.ensure((size_t)inst * (m ? m : 1) * 2)))
+    return fail(c, HBX_E_OUT_OF_MEMORY, "decode: leaf hashes");
+  if (d_leaf_hash) {
+    const uint32_t words = inst * n * 8;
+    hipLaunchKernelGGL(k_import_leaf_hashes, dim3((words + 255) / 256), dim3(256), 0, s, d_leaf_hash, d_present,
+                       inst * n, c->leaf_hash.as<uint32_t>());
+    if (m) {  // Coding::Trivial reconstructs nothing: every shard is present or the status is an error
+      hipLaunchKernelGGL(k_missing_slots, dim3(inst), dim3(64), 0, s, d_present, n, d_status, m,
+                         c->leaf_slots.as<uint16_t>());
+      leaves(c->leaf_slots.as<uint16_t>(), m);
+    }
+  }
+  if (!d_leaf_hash) leaves(nullptr, 0u);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_merkle_tree, dim3(inst), dim3(128), 0, s, c->leaf_hash.as<uint32_t>(), n, c->roots.as<uint8_t>(),
+                     (uint8_t*)nullptr, c->merkle);
+  hipLaunchKernelGGL(k_root_check, dim3((inst + 63) / 64), dim3(64), 0, s, c->roots.as<uint8_t>(), d_root_expect, inst,
+                     d_status);
+  glue();
+  HIPCHK(c, hipGetLastError());
+  return HBX_OK;
+}
+
+// The host descriptors of a call (rg_desc per instance, and the call's other host arrays) are
+// laid out in the context's pinned staging buffer and uploaded with one asynchronous copy on the
+// call's stream, so the caller's arrays are consumed at return and nothing waits for the device
+// -- except a later staged call, which waits for the previous upload (not the previous kernels)
+// before it rewrites the staging, and rs_setup's one-off synchronisation per (k, m).  The same
+// staging carries an add's items and tile list and the column combine's list.
+// One call's staging as sub-ranges of `sizes` bytes, each starting 8 bytes aligned: fill host<T>(i),
+// upload(s), hand dev<T>(i) to the kernels; both go by the one offset of range i.
+struct staging {
+  hbx_ctx* c;
+  size_t off[5], bytes = 0;
+  uint8_t* pin = nullptr;  // nullptr: out of memory
+  staging(hbx_ctx* c_, std::initializer_list<size_t> sizes) : c(c_) {
+    size_t* o = off;
+    for (size_t b : sizes) bytes = (*o++ = (bytes + 7) & ~(size_t)7) + b;
+    if (c->rg_ev.recorded && hipEventSynchronize(c->rg_ev.e) != hipSuccess) return;
+    c->rg_ev.recorded = false;
+    if (c->rg_pin.ensure(bytes) && c->rg_ev.create() == hipSuccess && c->rg_dev.ensure(bytes))
+      pin = static_cast<uint8_t*>(c->rg_pin.p);
+  }
+  template <class T>
+  T* host(int i) const {
+    return reinterpret_cast<T*>(pin + off[i]);
+  }
+  int upload(hipStream_t s) const {
+    HIPCHK(c, hipMemcpyAsync(c->rg_dev.p, c->rg_pin.p, bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipEventRecord(c->rg_ev.e, s));
+    c->rg_ev.recorded = true;
+    return HBX_OK;
+  }
+  template <class T>
+  const T* dev(int i) const {
+    return reinterpret_cast<const T*>(c->rg_dev.as<uint8_t>() + off[i]);
+  }
+};
+
+// The long values of a proof list (more than 256 bytes: Echo proofs of real shards) get their leaf
+// digests from the leaf kernels, in blocks of one length each (bcplan.hpp group_long).  The digests
+// land at the proof's own index, so neither the proofs' order nor the grouping shows in the results.
+// Ranges 0 to 2 of the call's staging: val_off u64[count + 1] | blk_len | blk_idx; 3, 4: the caller's.
+struct long_values {
+  uint32_t lanes;
+  std::vector<uint32_t> blk_len, blk_idx;
+  long_values(const hbx_ctx* c, const uint64_t* val_off, uint32_t count, uint64_t max_value) : lanes(leaf_lanes(c)) {
+    hbx_bcplan::group_long(val_off, count, lanes, max_value, blk_len, blk_idx);
+  }
+  size_t blocks() const { return blk_len.size(); }
+  staging stage(hbx_ctx* c, const uint64_t* val_off, uint32_t count, size_t more3 = 0, size_t more4 = 0) const {
+    const size_t b0 = (size_t)(count + 1) * 8, b1 = blocks() * 4, b2 = blocks() * lanes * 4;
+    const staging st = more3 || more4 ? staging(c, {b0, b1, b2, more3, more4}) : staging(c, {b0, b1, b2});
+    if (st.pin) memcpy(st.host<uint64_t>(0), val_off, b0);
+    if (st.pin && b1) memcpy(st.host<uint32_t>(1), blk_len.data(), b1);
+    if (st.pin && b1) memcpy(st.host<uint32_t>(2), blk_idx.data(), b2);
+    return st;
+  }
+  // one block of the family's kernel per hash block; `tail` = the kernels' arguments after blk_idx
+  template <class K, class... A>
+  void hash(hbx_ctx* c, hipStream_t s, const staging& st, K sha256, K sha3, const uint8_t* d_values, A... tail) const {
+    if (blocks())
+      leaf_blocks(c, s, sha256, sha3, dim3((unsigned)blocks()), d_values, st.dev<uint64_t>(0), st.dev<uint32_t>(1),
+                  st.dev<uint32_t>(2), tail...);
+  }
+};
 
 extern "C" {
 
@@ -1299,13 +1430,8 @@ int hbx_merkle_validate_d(hbx_ctx* c, const uint8_t* d_values, uint32_t vlen, co
   if (vlen > 256) {
     if (!c->val_digest.ensure((size_t)nproofs * 32))
       return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_merkle_validate_d: out of device memory");
-    timed t_(c, HBX_K_MERKLE_LEAVES, s);
-    if (c->merkle == HBX_MERKLE_SHA256)
-      hipLaunchKernelGGL(k_merkle_leaves_sha256, dim3((nproofs + 63) / 64, 1), dim3(128), 0, s, d_values + 1, (size_t)0,
-                         nproofs, vlen - 1, c->val_digest.as<uint32_t>(), (const uint16_t*)nullptr, 0u, vlen);
-    else
-      hipLaunchKernelGGL(k_merkle_leaves_sha3, dim3((nproofs + 31) / 32, 1), dim3(64), 0, s, d_values + 1, (size_t)0,
-                         nproofs, vlen - 1, c->val_digest.as<uint32_t>(), (const uint16_t*)nullptr, 0u, vlen);
+    leaf_digests(c, s, k_merkle_leaves_sha256, k_merkle_leaves_sha3, nproofs, 1u, d_values + 1, (size_t)0, nproofs,
+                 vlen - 1, c->val_digest.as<uint32_t>(), (const uint16_t*)nullptr, 0u, vlen);
     HIPCHK(c, hipGetLastError());
     vdigest = c->val_digest.as<uint32_t>();
   }
@@ -1343,8 +1469,7 @@ int hbx_merkle_proofs_d(hbx_ctx* c, const uint8_t* d_nodes, uint32_t n, const ui
   return HBX_OK;
 }
 
-// decode_from_shards + glue for `inst` instances; with d_leaf_hash the present shards' leaf digests
-// are taken from it (validated Echo proofs) and only the reconstructed shards are hashed.
+// decode_from_shards + glue for `inst` instances of uniform rows.
 static int broadcast_decode(hbx_ctx* c, uint8_t* d_shards, const uint8_t* d_present, const uint8_t* d_leaf_hash,
                             const uint8_t* d_root_expect, uint32_t inst, uint32_t k, uint32_t m, uint32_t L,
                             uint8_t* d_out, uint64_t out_stride, uint64_t* d_out_len, int32_t* d_status, void* stream) {
@@ -1360,42 +1485,13 @@ static int broadcast_decode(hbx_ctx* c, uint8_t* d_shards, const uint8_t* d_pres
   if (rc) return rc;
   rc = rs_reconstruct(c, d_shards, d_present, inst, k, m, L, d_status, s);
   if (rc) return rc;
-  if (!c->roots.ensure((size_t)inst * 32)) return fail(c, HBX_E_OUT_OF_MEMORY, "decode: roots");
-  if (d_leaf_hash) {
-    const uint32_t n = k + m;
-    if (n > (uint32_t)RS_MAX_N) return fail(c, HBX_E_INVALID_ARG, "merkle: need 1 <= n <= 256");
-    if (!c->leaf_hash.ensure((size_t)inst * n * 32) || !c->leaf_slots.ensure((size_t)inst * (m ? m : 1) * 2))
-      return fail(c, HBX_E_OUT_OF_MEMORY, "decode: leaf hashes");
-    const uint32_t words = inst * n * 8;
-    hipLaunchKernelGGL(k_import_leaf_hashes, dim3((words + 255) / 256), dim3(256), 0, s, d_leaf_hash, d_present,
-                       inst * n, c->leaf_hash.as<uint32_t>());
-    if (m) {  // Coding::Trivial reconstructs nothing: every shard is present or the status is an error
-      hipLaunchKernelGGL(k_missing_slots, dim3(inst), dim3(64), 0, s, d_present, n, d_status, m,
-                         c->leaf_slots.as<uint16_t>());
-      timed t_(c, HBX_K_MERKLE_LEAVES, s);
-      if (c->merkle == HBX_MERKLE_SHA256)
-        hipLaunchKernelGGL(k_merkle_leaves_sha256, dim3((m + 63) / 64, inst), dim3(128), 0, s, d_shards,
-                           (size_t)n * L, n, L, c->leaf_hash.as<uint32_t>(), c->leaf_slots.as<uint16_t>(), m, 0u);
-      else
-        hipLaunchKernelGGL(k_merkle_leaves_sha3, dim3((m + 31) / 32, inst), dim3(64), 0, s, d_shards, (size_t)n * L,
-                           n, L, c->leaf_hash.as<uint32_t>(), c->leaf_slots.as<uint16_t>(), m, 0u);
-    }
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(k_merkle_tree, dim3(inst), dim3(128), 0, s, c->leaf_hash.as<uint32_t>(), n,
-                       c->roots.as<uint8_t>(), (uint8_t*)nullptr, c->merkle);
-    HIPCHK(c, hipGetLastError());
-  } else {
-    rc = merkle_roots(c, d_shards, inst, k + m, L, c->roots.as<uint8_t>(), s);
-    if (rc) return rc;
-  }
-  hipLaunchKernelGGL(k_root_check, dim3((inst + 63) / 64), dim3(64), 0, s, c->roots.as<uint8_t>(), d_root_expect, inst,
-                     d_status);
-  HIPCHK(c, hipGetLastError());
-  const uint64_t glue_blocks = ((uint64_t)k * L + 4095) / 4096;
-  hipLaunchKernelGGL(k_glue, dim3((unsigned)glue_blocks, inst), dim3(256), 0, s, d_shards, (size_t)(k + m) * L, k, L, d_out,
-                     (size_t)out_stride, d_out_len, d_status);
-  HIPCHK(c, hipGetLastError());
-  return HBX_OK;
+  const uint32_t n = k + m;
+  const dim3 glue_grid((unsigned)(((uint64_t)k * L + 4095) / 4096), inst);
+  return decode_tail(
+      c, d_present, d_leaf_hash, d_root_expect, inst, n, m, d_status, s,
+      [&](const uint16_t* slots, uint32_t nslots) { leaves_uniform(c, s, d_shards, inst, n, L, slots, nslots); },
+      [&] { hipLaunchKernelGGL(k_glue, glue_grid, dim3(256), 0, s, d_shards, (size_t)n * L, k, L, d_out,
+                               (size_t)out_stride, d_out_len, d_status); });
 }
 
 int hbx_broadcast_decode_d(hbx_ctx* c, uint8_t* d_shards, const uint8_t* d_present, const uint8_t* d_root_expect,
@@ -1412,27 +1508,6 @@ int hbx_broadcast_decode_leaves_d(hbx_ctx* c, uint8_t* d_shards, const uint8_t* 
   if (!d_leaf_hash) return fail(c, HBX_E_INVALID_ARG, "hbx_broadcast_decode_leaves_d: d_leaf_hash is NULL");
   return broadcast_decode(c, d_shards, d_present, d_leaf_hash, d_root_expect, inst, k, m, L, d_out, out_stride,
                           d_out_len, d_status, stream);
-}
-
-// ---- Broadcast, ragged forms (include/hbx.h): per-instance shard lengths in one call -----------
-// The host descriptors of a call (rg_desc per instance, and the call's other host arrays) are
-// laid out in the context's pinned staging buffer and uploaded with one asynchronous copy on the
-// call's stream, so the caller's arrays are consumed at return and nothing waits for the device
-// -- except a later staged call, which waits for the previous upload (not the previous kernels)
-// before it rewrites the staging, and rs_setup's one-off synchronisation per (k, m).  The same
-// staging carries an add's items and tile list and the column combine's list.
-static uint8_t* staging_begin(hbx_ctx* c, size_t bytes) {
-  if (c->rg_ev.recorded && hipEventSynchronize(c->rg_ev.e) != hipSuccess) return nullptr;
-  c->rg_ev.recorded = false;
-  if (!c->rg_pin.ensure(bytes) || c->rg_ev.create() != hipSuccess || !c->rg_dev.ensure(bytes)) return nullptr;
-  return static_cast<uint8_t*>(c->rg_pin.p);
-}
-
-static int staging_upload(hbx_ctx* c, size_t bytes, hipStream_t s) {
-  HIPCHK(c, hipMemcpyAsync(c->rg_dev.p, c->rg_pin.p, bytes, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipEventRecord(c->rg_ev.e, s));
-  c->rg_ev.recorded = true;
-  return HBX_OK;
 }
 
 // Every listed index is below `bound` and listed once (before anything is launched); `name` is the
@@ -1473,15 +1548,15 @@ static int add_plan_rejected(hbx_ctx* c, int plan_rc, const char* fn, const char
 static int add_stage(hbx_ctx* c, const char* fn, const uint32_t* row, const uint32_t* sender, uint32_t count,
                      const std::vector<hbx_addplan::tile>& tiles, hipStream_t s, const uint2** d_items,
                      const uint2** d_tiles) {
-  const size_t items_bytes = (size_t)count * sizeof(uint2), tiles_bytes = tiles.size() * sizeof(uint2);
-  uint8_t* pin = staging_begin(c, items_bytes + tiles_bytes);
-  if (!pin) return fail(c, HBX_E_OUT_OF_MEMORY, "%s: out of memory (staging)", fn);
-  uint2* it = reinterpret_cast<uint2*>(pin);
+  const size_t tiles_bytes = tiles.size() * sizeof(uint2);
+  staging st(c, {(size_t)count * sizeof(uint2), tiles_bytes});
+  if (!st.pin) return fail(c, HBX_E_OUT_OF_MEMORY, "%s: out of memory (staging)", fn);
+  uint2* it = st.host<uint2>(0);
   for (uint32_t k = 0; k < count; k++) it[k] = make_uint2(row[k], sender[k]);
-  if (tiles_bytes) memcpy(pin + items_bytes, tiles.data(), tiles_bytes);
-  if (int rc = staging_upload(c, items_bytes + tiles_bytes, s)) return rc;
-  *d_items = c->rg_dev.as<uint2>();
-  *d_tiles = reinterpret_cast<const uint2*>(c->rg_dev.as<uint8_t>() + items_bytes);
+  if (tiles_bytes) memcpy(st.host<uint2>(1), tiles.data(), tiles_bytes);
+  if (int rc = st.upload(s)) return rc;
+  *d_items = st.dev<uint2>(0);
+  *d_tiles = st.dev<uint2>(1);
   return HBX_OK;
 }
 
@@ -1505,36 +1580,54 @@ static int add_host(hbx_ctx* c, const char* fn, add_state hbx_ctx::*state, size_
   return HBX_OK;
 }
 
-// The descriptor rules of include/hbx.h; max_len = the longest shard.
+// ---- Broadcast, ragged forms (include/hbx.h): per-instance shard lengths in one call -----------
+// The descriptor rules (bcplan.hpp check_rows) as entry point `fn`'s error; max_len = the longest shard.
 static int rg_check(hbx_ctx* c, const char* fn, uint64_t buf_bytes, const uint64_t* off, const uint32_t* len,
                     const uint32_t* pitch, uint32_t inst, uint32_t n, uint32_t* max_len) {
   if (!off || !len || !pitch || inst == 0 || n == 0) return fail(c, HBX_E_INVALID_ARG, "%s: bad args", fn);
-  uint32_t mx = 0;
-  for (uint32_t q = 0; q < inst; q++) {
-    if (off[q] % 4 || pitch[q] % 4)
+  uint32_t bad[2] = {0, 0};
+  const uint32_t& q = bad[0];
+  switch (hbx_bcplan::check_rows(buf_bytes, off, len, pitch, inst, n, max_len, bad)) {
+    case hbx_bcplan::ROWS_UNALIGNED:
       return fail(c, HBX_E_INVALID_ARG, "%s: instance %u: off %llu and pitch %u must be multiples of 4", fn, q,
                   (unsigned long long)off[q], pitch[q]);
-    if (len[q] == 0 || pitch[q] < len[q])
+    case hbx_bcplan::ROWS_BAD_LEN:
       return fail(c, HBX_E_INVALID_ARG, "%s: instance %u: need pitch %u >= len %u >= 1", fn, q, pitch[q], len[q]);
-    if (off[q] > buf_bytes || (uint64_t)n * pitch[q] > buf_bytes - off[q])
+    case hbx_bcplan::ROWS_PAST_END:
       return fail(c, HBX_E_INVALID_ARG, "%s: instance %u: rows [%llu, +%u x %u) end past the buffer (%llu bytes)", fn, q,
                   (unsigned long long)off[q], n, pitch[q], (unsigned long long)buf_bytes);
-    if (len[q] > mx) mx = len[q];
+    case hbx_bcplan::ROWS_OVERLAP:
+      return fail(c, HBX_E_INVALID_ARG, "%s: instances %u and %u overlap", fn, bad[0], bad[1]);
+    default:
+      return HBX_OK;
   }
-  std::vector<uint32_t> order(inst);
-  for (uint32_t q = 0; q < inst; q++) order[q] = q;
-  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return off[a] < off[b]; });
-  for (uint32_t r = 1; r < inst; r++) {
-    const uint32_t a = order[r - 1], b = order[r];
-    if (off[b] < off[a] + (uint64_t)n * pitch[a])
-      return fail(c, HBX_E_INVALID_ARG, "%s: instances %u and %u overlap", fn, a, b);
-  }
-  *max_len = mx;
-  return HBX_OK;
 }
 
-static void rg_fill(rg_desc* d, const uint64_t* off, const uint32_t* len, const uint32_t* pitch, uint32_t inst) {
+static int bc_plan_rejected(hbx_ctx* c, int rc, const char* fn) {
+  switch (rc) {
+    case hbx_bcplan::PLAN_BAD_INST:
+      return fail(c, HBX_E_INVALID_ARG, "%s: an instance is not below the store's %u", fn, c->bc_inst);
+    case hbx_bcplan::PLAN_BAD_SENDER:
+      return fail(c, HBX_E_INVALID_ARG, "%s: a sender is not below n = %u", fn, c->bc_k + c->bc_m);
+    case hbx_bcplan::PLAN_DUPLICATE:
+      return fail(c, HBX_E_INVALID_ARG, "%s: the same entry twice in one call", fn);
+    case hbx_bcplan::PLAN_BAD_OFFSETS:
+      return fail(c, HBX_E_INVALID_ARG, "%s: val_off is not a non-decreasing offset list within the values", fn);
+    case hbx_bcplan::PLAN_BAD_LEN:
+      return fail(c, HBX_E_INVALID_ARG, "%s: need 1 <= len <= max_shard_len = %u", fn, c->bc_max);
+    case hbx_bcplan::PLAN_NO_ROOM:
+      return fail(c, HBX_E_INVALID_ARG, "%s: an attempt has no room of its own for k len - 4 output bytes", fn);
+    default:
+      return HBX_OK;
+  }
+}
+
+// The descriptors into range 0 of the call's staging, and the staging up.
+static int rg_upload(const staging& st, const uint64_t* off, const uint32_t* len, const uint32_t* pitch, uint32_t inst,
+                     hipStream_t s) {
+  rg_desc* d = st.host<rg_desc>(0);
   for (uint32_t q = 0; q < inst; q++) d[q] = rg_desc{off[q], len[q], pitch[q]};
+  return st.upload(s);
 }
 
 // One ragged coding pass: the triple byte-permute kernel, tiled by output count as rs_code tiles it
@@ -1544,83 +1637,59 @@ static void rs_code_rg(hbx_ctx* c, uint8_t* d_buf, const rg_desc* d_desc, uint32
   timed t_(c, HBX_K_RS_CODE, s);
   if (no == 0) no = 1;
   const uint32_t Ld = (max_len + 3) / 4;
-  switch (rs_tile3(k, no)) {
-#define HBX_RS_TILE3RG(c3)                                                                                            \
-  hipLaunchKernelGGL((k_rs_code_perm3_rg<c3, 2>), dim3((Ld + 511) / 512, inst, (no + c3 - 1) / c3), dim3(256),         \
-                     rs_perm3_lds_bytes(k, c3), s, d_buf, d_desc, k, jobs, ptab, job_stride);                          \
-  break;
-    case 42: HBX_RS_TILE3RG(42)
-    case 28: HBX_RS_TILE3RG(28)
-    case 14: HBX_RS_TILE3RG(14)
-    case 12: HBX_RS_TILE3RG(12)
-    default: HBX_RS_TILE3RG(21)
-#undef HBX_RS_TILE3RG
-  }
+  rs_with_tile(rs_tile3(k, no), [&](auto tile) {
+    constexpr int c3 = decltype(tile)::value;
+    hipLaunchKernelGGL((k_rs_code_perm3_rg<c3, 2>), dim3((Ld + 511) / 512, inst, (no + c3 - 1) / c3), dim3(256),
+                       rs_perm3_lds_bytes(k, c3), s, d_buf, d_desc, k, jobs, ptab, job_stride);
+  });
 }
 
 static int rs_reconstruct_rg(hbx_ctx* c, uint8_t* d_buf, const rg_desc* d_desc, uint32_t max_len,
                              const uint8_t* d_present, uint32_t inst, uint32_t k, uint32_t m, int32_t* d_status,
                              hipStream_t s) {
-  const size_t tab = (size_t)inst * RS_MAX_N * k;
-  if (!c->rs_jobs_d.ensure((size_t)inst * sizeof(rs_job)) || !c->rs_jobs_p.ensure((size_t)inst * sizeof(rs_job)) ||
-      !c->rs_coef_d.ensure(tab * 2) || !c->rs_coef_p.ensure(tab * 2) || !c->rs_ptab_d.ensure(tab * sizeof(gf_ptab)) ||
-      !c->rs_ptab_p.ensure(tab * sizeof(gf_ptab)))
-    return fail(c, HBX_E_OUT_OF_MEMORY, "rs_reconstruct: out of device memory");
-  hipLaunchKernelGGL(k_rs_setup_reconstruct, dim3(inst), dim3(256), 0, s, d_present, k, m, c->rs_enc.as<uint8_t>(),
-                     c->gf_log.as<uint16_t>(), c->gf_exp.as<uint8_t>(), c->rs_jobs_d.as<rs_job>(),
-                     c->rs_coef_d.as<uint16_t>(), c->rs_jobs_p.as<rs_job>(), c->rs_coef_p.as<uint16_t>(), d_status);
-  const dim3 tg((RS_MAX_N * k + 255) / 256, inst);
-  hipLaunchKernelGGL(k_rs_perm_tables, tg, dim3(256), 0, s, c->rs_jobs_d.as<rs_job>(), c->rs_coef_d.as<uint16_t>(), k,
-                     c->gf_log.as<uint16_t>(), c->gf_exp.as<uint8_t>(), c->rs_ptab_d.as<gf_ptab>());
-  hipLaunchKernelGGL(k_rs_perm_tables, tg, dim3(256), 0, s, c->rs_jobs_p.as<rs_job>(), c->rs_coef_p.as<uint16_t>(), k,
-                     c->gf_log.as<uint16_t>(), c->gf_exp.as<uint8_t>(), c->rs_ptab_p.as<gf_ptab>());
-  HIPCHK(c, hipGetLastError());
+  if (int rc = rs_reconstruct_tables(c, d_present, inst, k, m, d_status, true, s)) return rc;
   rs_code_rg(c, d_buf, d_desc, max_len, k, inst, c->rs_jobs_d.as<rs_job>(), c->rs_ptab_d.as<gf_ptab>(), 1u, (m + 1) / 2, s);
   rs_code_rg(c, d_buf, d_desc, max_len, k, inst, c->rs_jobs_p.as<rs_job>(), c->rs_ptab_p.as<gf_ptab>(), 1u, (m + 1) / 2, s);
   HIPCHK(c, hipGetLastError());
   return HBX_OK;
 }
 
-// Leaf digests (all leaves, or the `nslots` listed per instance) into c->leaf_hash, then the trees.
-static int merkle_tree_rg(hbx_ctx* c, const uint8_t* d_buf, const rg_desc* d_desc, uint32_t inst, uint32_t n,
-                          const uint16_t* slots, uint32_t nslots, bool leaves, uint8_t* d_roots, uint8_t* d_nodes,
+// Ragged rows' leaf digests into c->leaf_hash: all n leaves, or the `nslots` listed per instance.
+static void leaves_rg(hbx_ctx* c, hipStream_t s, const uint8_t* d_buf, const rg_desc* d_desc, uint32_t inst, uint32_t n,
+                      const uint16_t* slots, uint32_t nslots) {
+  leaf_digests(c, s, k_merkle_leaves_sha256_rg, k_merkle_leaves_sha3_rg, slots ? nslots : n, inst, d_buf, d_desc, n,
+               c->leaf_hash.as<uint32_t>(), slots, nslots);
+}
+
+// decode_tail on rg_desc rows; d_out_off = the payloads' offsets in d_out.
+static int decode_tail_rg(hbx_ctx* c, uint8_t* d_buf, const rg_desc* d_desc, uint32_t max_len, const uint8_t* d_present,
+                          const uint8_t* d_leaf_hash, const uint8_t* d_root_expect, uint32_t inst, uint32_t k, uint32_t m,
+                          uint8_t* d_out, const uint64_t* d_out_off, uint64_t* d_out_len, int32_t* d_status,
                           hipStream_t s) {
-  if (leaves) {
-    timed t_(c, HBX_K_MERKLE_LEAVES, s);
-    const uint32_t cnt = slots ? nslots : n;
-    if (c->merkle == HBX_MERKLE_SHA256)
-      hipLaunchKernelGGL(k_merkle_leaves_sha256_rg, dim3((cnt + 63) / 64, inst), dim3(128), 0, s, d_buf, d_desc, n,
-                         c->leaf_hash.as<uint32_t>(), slots, nslots);
-    else
-      hipLaunchKernelGGL(k_merkle_leaves_sha3_rg, dim3((cnt + 31) / 32, inst), dim3(64), 0, s, d_buf, d_desc, n,
-                         c->leaf_hash.as<uint32_t>(), slots, nslots);
-  }
-  HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(k_merkle_tree, dim3(inst), dim3(128), 0, s, c->leaf_hash.as<uint32_t>(), n, d_roots, d_nodes,
-                     c->merkle);
-  HIPCHK(c, hipGetLastError());
-  return HBX_OK;
+  const dim3 glue_grid((unsigned)(((uint64_t)k * max_len + 4095) / 4096), inst);
+  return decode_tail(
+      c, d_present, d_leaf_hash, d_root_expect, inst, k + m, m, d_status, s,
+      [&](const uint16_t* slots, uint32_t nslots) { leaves_rg(c, s, d_buf, d_desc, inst, k + m, slots, nslots); },
+      [&] { hipLaunchKernelGGL(k_glue_rg, glue_grid, dim3(256), 0, s, d_buf, d_desc, k, d_out, d_out_off, d_out_len,
+                               d_status); });
 }
 
 int hbx_rs_encode_ragged_d(hbx_ctx* c, uint8_t* d_buf, uint64_t buf_bytes, const uint64_t* off, const uint32_t* len,
                            const uint32_t* pitch, uint32_t inst, uint32_t k, uint32_t m, void* stream) {
   if (!c || !d_buf) return fail(c, HBX_E_INVALID_ARG, "hbx_rs_encode_ragged_d: bad args");
-  if (k == 0 || k > (uint32_t)RS_MAX_K || k + m > (uint32_t)RS_MAX_N)
-    return fail(c, HBX_E_INVALID_ARG, "rs: need 1 <= k <= %d and k + m <= %d (k=%u m=%u)", RS_MAX_K, RS_MAX_N, k, m);
   uint32_t max_len = 0;
-  int rc = rg_check(c, "hbx_rs_encode_ragged_d", buf_bytes, off, len, pitch, inst, k + m, &max_len);
+  int rc = rs_bounds(c, k, m);
+  if (!rc) rc = rg_check(c, "hbx_rs_encode_ragged_d", buf_bytes, off, len, pitch, inst, k + m, &max_len);
   if (rc) return rc;
   HBX_ENTER(c, stream);
   if (m == 0) return HBX_OK;  // Coding::Trivial
   rc = rs_setup(c, k, m, s);
   if (rc) return rc;
-  const size_t bytes = (size_t)inst * sizeof(rg_desc);
-  uint8_t* h = staging_begin(c, bytes);
-  if (!h) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_rs_encode_ragged_d: descriptor staging");
-  rg_fill(reinterpret_cast<rg_desc*>(h), off, len, pitch, inst);
-  rc = staging_upload(c, bytes, s);
+  staging st(c, {(size_t)inst * sizeof(rg_desc)});
+  if (!st.pin) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_rs_encode_ragged_d: descriptor staging");
+  rc = rg_upload(st, off, len, pitch, inst, s);
   if (rc) return rc;
-  rs_code_rg(c, d_buf, c->rg_dev.as<rg_desc>(), max_len, k, inst, c->rs_enc_job.as<rs_job>(),
+  rs_code_rg(c, d_buf, st.dev<rg_desc>(0), max_len, k, inst, c->rs_enc_job.as<rs_job>(),
              c->rs_enc_ptab.as<gf_ptab>(), 0u, m, s);
   HIPCHK(c, hipGetLastError());
   return HBX_OK;
@@ -1630,21 +1699,18 @@ int hbx_rs_reconstruct_ragged_d(hbx_ctx* c, uint8_t* d_buf, uint64_t buf_bytes, 
                                 const uint32_t* len, const uint32_t* pitch, const uint8_t* d_present, uint32_t inst,
                                 uint32_t k, uint32_t m, int32_t* d_status, void* stream) {
   if (!c || !d_buf || !d_present || !d_status) return fail(c, HBX_E_INVALID_ARG, "hbx_rs_reconstruct_ragged_d: bad args");
-  if (k == 0 || k > (uint32_t)RS_MAX_K || k + m > (uint32_t)RS_MAX_N)
-    return fail(c, HBX_E_INVALID_ARG, "rs: need 1 <= k <= %d and k + m <= %d (k=%u m=%u)", RS_MAX_K, RS_MAX_N, k, m);
   uint32_t max_len = 0;
-  int rc = rg_check(c, "hbx_rs_reconstruct_ragged_d", buf_bytes, off, len, pitch, inst, k + m, &max_len);
+  int rc = rs_bounds(c, k, m);
+  if (!rc) rc = rg_check(c, "hbx_rs_reconstruct_ragged_d", buf_bytes, off, len, pitch, inst, k + m, &max_len);
   if (rc) return rc;
   HBX_ENTER(c, stream);
   rc = rs_setup(c, k, m, s);
   if (rc) return rc;
-  const size_t bytes = (size_t)inst * sizeof(rg_desc);
-  uint8_t* h = staging_begin(c, bytes);
-  if (!h) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_rs_reconstruct_ragged_d: descriptor staging");
-  rg_fill(reinterpret_cast<rg_desc*>(h), off, len, pitch, inst);
-  rc = staging_upload(c, bytes, s);
+  staging st(c, {(size_t)inst * sizeof(rg_desc)});
+  if (!st.pin) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_rs_reconstruct_ragged_d: descriptor staging");
+  rc = rg_upload(st, off, len, pitch, inst, s);
   if (rc) return rc;
-  return rs_reconstruct_rg(c, d_buf, c->rg_dev.as<rg_desc>(), max_len, d_present, inst, k, m, d_status, s);
+  return rs_reconstruct_rg(c, d_buf, st.dev<rg_desc>(0), max_len, d_present, inst, k, m, d_status, s);
 }
 
 int hbx_merkle_build_ragged_d(hbx_ctx* c, const uint8_t* d_buf, uint64_t buf_bytes, const uint64_t* off,
@@ -1658,14 +1724,16 @@ int hbx_merkle_build_ragged_d(hbx_ctx* c, const uint8_t* d_buf, uint64_t buf_byt
   HBX_ENTER(c, stream);
   if (!c->leaf_hash.ensure((size_t)inst * n * 32) || (!d_roots && !c->roots.ensure((size_t)inst * 32)))
     return fail(c, HBX_E_OUT_OF_MEMORY, "merkle: leaf hashes");
-  const size_t bytes = (size_t)inst * sizeof(rg_desc);
-  uint8_t* h = staging_begin(c, bytes);
-  if (!h) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_merkle_build_ragged_d: descriptor staging");
-  rg_fill(reinterpret_cast<rg_desc*>(h), off, len, pitch, inst);
-  rc = staging_upload(c, bytes, s);
+  staging st(c, {(size_t)inst * sizeof(rg_desc)});
+  if (!st.pin) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_merkle_build_ragged_d: descriptor staging");
+  rc = rg_upload(st, off, len, pitch, inst, s);
   if (rc) return rc;
-  return merkle_tree_rg(c, d_buf, c->rg_dev.as<rg_desc>(), inst, n, nullptr, 0, true,
-                        d_roots ? d_roots : c->roots.as<uint8_t>(), d_nodes, s);
+  leaves_rg(c, s, d_buf, st.dev<rg_desc>(0), inst, n, nullptr, 0);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_merkle_tree, dim3(inst), dim3(128), 0, s, c->leaf_hash.as<uint32_t>(), n,
+                     d_roots ? d_roots : c->roots.as<uint8_t>(), d_nodes, c->merkle);
+  HIPCHK(c, hipGetLastError());
+  return HBX_OK;
 }
 
 int hbx_merkle_validate_ragged_d(hbx_ctx* c, const uint8_t* d_values, uint64_t values_bytes, const uint64_t* val_off,
@@ -1675,60 +1743,23 @@ int hbx_merkle_validate_ragged_d(hbx_ctx* c, const uint8_t* d_values, uint64_t v
   if (!c || !d_values || !val_off || !d_node_hash || !d_sib_hash || !d_sides || !d_depth || !d_root || !d_sender ||
       !d_valid || nproofs == 0)
     return fail(c, HBX_E_INVALID_ARG, "hbx_merkle_validate_ragged_d: bad args");
-  for (uint32_t j = 0; j < nproofs; j++)
-    if (val_off[j + 1] < val_off[j] || val_off[j + 1] - val_off[j] > 0xFFFFFFFFull)
-      return fail(c, HBX_E_INVALID_ARG, "hbx_merkle_validate_ragged_d: val_off[%u..] is not a non-decreasing offset list", j);
-  if (val_off[nproofs] > values_bytes)
+  uint32_t bad = 0;
+  if (hbx_bcplan::check_offsets(val_off, nproofs, values_bytes, &bad)) {
+    if (bad < nproofs)
+      return fail(c, HBX_E_INVALID_ARG, "hbx_merkle_validate_ragged_d: val_off[%u..] is not a non-decreasing offset list", bad);
     return fail(c, HBX_E_INVALID_ARG, "hbx_merkle_validate_ragged_d: val_off ends at %llu, past the %llu value bytes",
                 (unsigned long long)val_off[nproofs], (unsigned long long)values_bytes);
+  }
   HBX_ENTER(c, stream);
-  // long values (more than 256 bytes: Echo proofs of real shards) get their leaf digests from the
-  // leaf kernels, in blocks of one length each: sorted by (length, index), every run of a length is
-  // cut into blocks of B lanes.  The digests land at the proof's own index, so neither the order
-  // of the proofs nor this grouping shows in the results.
-  const uint32_t B = c->merkle == HBX_MERKLE_SHA256 ? 64 : 32;
-  std::vector<uint64_t> lng;  // (length << 32) | index of every long value
-  for (uint32_t j = 0; j < nproofs; j++)
-    if (val_off[j + 1] - val_off[j] > 256) lng.push_back(((val_off[j + 1] - val_off[j]) << 32) | j);
-  if (!std::is_sorted(lng.begin(), lng.end())) std::sort(lng.begin(), lng.end());
-  std::vector<uint32_t> blk_len, blk_idx;
-  blk_idx.reserve(lng.size() + B);
-  for (size_t i = 0; i < lng.size();) {
-    size_t e = i;
-    while (e < lng.size() && e - i < B && (lng[e] >> 32) == (lng[i] >> 32)) e++;
-    blk_len.push_back((uint32_t)(lng[i] >> 32));
-    for (size_t q = 0; q < B; q++) blk_idx.push_back(i + q < e ? (uint32_t)lng[i + q] : VAL_NONE);
-    i = e;
-  }
-  const size_t nblk = blk_len.size();
-  const size_t o_len = (size_t)(nproofs + 1) * 8, o_idx = o_len + ((nblk * 4 + 7) & ~(size_t)7),
-               bytes = o_idx + nblk * B * 4;
-  uint8_t* h = staging_begin(c, bytes);
-  if (!h || (nblk && !c->val_digest.ensure((size_t)nproofs * 32)))
+  const long_values lv(c, val_off, nproofs, 0);
+  const staging st = lv.stage(c, val_off, nproofs);
+  if (!st.pin || (lv.blocks() && !c->val_digest.ensure((size_t)nproofs * 32)))
     return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_merkle_validate_ragged_d: out of memory");
-  memcpy(h, val_off, o_len);
-  if (nblk) {
-    memcpy(h + o_len, blk_len.data(), nblk * 4);
-    memcpy(h + o_idx, blk_idx.data(), nblk * B * 4);
-  }
-  int rc = staging_upload(c, bytes, s);
-  if (rc) return rc;
-  const uint8_t* dv = c->rg_dev.as<uint8_t>();
-  const uint64_t* d_off = reinterpret_cast<const uint64_t*>(dv);
-  if (nblk) {
-    timed t_(c, HBX_K_MERKLE_LEAVES, s);
-    if (c->merkle == HBX_MERKLE_SHA256)
-      hipLaunchKernelGGL(k_merkle_values_sha256_rg, dim3((unsigned)nblk), dim3(128), 0, s, d_values, d_off,
-                         reinterpret_cast<const uint32_t*>(dv + o_len), reinterpret_cast<const uint32_t*>(dv + o_idx),
-                         c->val_digest.as<uint32_t>());
-    else
-      hipLaunchKernelGGL(k_merkle_values_sha3_rg, dim3((unsigned)nblk), dim3(64), 0, s, d_values, d_off,
-                         reinterpret_cast<const uint32_t*>(dv + o_len), reinterpret_cast<const uint32_t*>(dv + o_idx),
-                         c->val_digest.as<uint32_t>());
-    HIPCHK(c, hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_merkle_validate_rg, dim3((nproofs + 63) / 64), dim3(64), 0, s, d_values, d_off, d_node_hash,
-                     d_sib_hash, d_sides, d_depth, d_root, d_sender, count, nproofs, d_valid, c->merkle,
+  if (int rc = st.upload(s)) return rc;
+  lv.hash(c, s, st, k_merkle_values_sha256_rg, k_merkle_values_sha3_rg, d_values, c->val_digest.as<uint32_t>());
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_merkle_validate_rg, dim3((nproofs + 63) / 64), dim3(64), 0, s, d_values, st.dev<uint64_t>(0),
+                     d_node_hash, d_sib_hash, d_sides, d_depth, d_root, d_sender, count, nproofs, d_valid, c->merkle,
                      c->val_digest.as<uint32_t>());
   HIPCHK(c, hipGetLastError());
   return HBX_OK;
@@ -1742,62 +1773,31 @@ int hbx_broadcast_decode_ragged_d(hbx_ctx* c, uint8_t* d_buf, uint64_t buf_bytes
   const char* fn = "hbx_broadcast_decode_ragged_d";
   if (!c || !d_buf || !d_present || !d_root_expect || !d_out || !out_off || !d_out_len || !d_status)
     return fail(c, HBX_E_INVALID_ARG, "%s: bad args", fn);
-  if (k == 0 || k > (uint32_t)RS_MAX_K || k + m > (uint32_t)RS_MAX_N)
-    return fail(c, HBX_E_INVALID_ARG, "rs: need 1 <= k <= %d and k + m <= %d (k=%u m=%u)", RS_MAX_K, RS_MAX_N, k, m);
-  const uint32_t n = k + m;
   uint32_t max_len = 0;
-  int rc = rg_check(c, fn, buf_bytes, off, len, pitch, inst, n, &max_len);
+  int rc = rs_bounds(c, k, m);
+  if (!rc) rc = rg_check(c, fn, buf_bytes, off, len, pitch, inst, k + m, &max_len);
   if (rc) return rc;
   // the payload length comes from the (untrusted) header: k len - 4 bytes is the most glue_shards
   // can take, so every instance's output range must hold that many, apart from the others'
-  std::vector<std::pair<uint64_t, uint64_t>> rng;
-  for (uint32_t q = 0; q < inst; q++) {
+  uint32_t q = 0;
+  if (hbx_bcplan::check_out(len, out_off, inst, k, out_bytes, &q)) {
+    if (q == inst) return fail(c, HBX_E_INVALID_ARG, "%s: output ranges overlap", fn);
     const uint64_t need = (uint64_t)k * len[q] >= 4 ? (uint64_t)k * len[q] - 4 : 0;
-    if (out_off[q] > out_bytes || need > out_bytes - out_off[q])
-      return fail(c, HBX_E_INVALID_ARG, "%s: instance %u: no room for k len - 4 = %llu bytes at out_off %llu of %llu", fn,
-                  q, (unsigned long long)need, (unsigned long long)out_off[q], (unsigned long long)out_bytes);
-    if (need) rng.emplace_back(out_off[q], out_off[q] + need);
+    return fail(c, HBX_E_INVALID_ARG, "%s: instance %u: no room for k len - 4 = %llu bytes at out_off %llu of %llu", fn,
+                q, (unsigned long long)need, (unsigned long long)out_off[q], (unsigned long long)out_bytes);
   }
-  std::sort(rng.begin(), rng.end());
-  for (size_t r = 1; r < rng.size(); r++)
-    if (rng[r].first < rng[r - 1].second) return fail(c, HBX_E_INVALID_ARG, "%s: output ranges overlap", fn);
   HBX_ENTER(c, stream);
   rc = rs_setup(c, k, m, s);
   if (rc) return rc;
-  if (!c->roots.ensure((size_t)inst * 32) || !c->leaf_hash.ensure((size_t)inst * n * 32) ||
-      !c->leaf_slots.ensure((size_t)inst * (m ? m : 1) * 2))
-    return fail(c, HBX_E_OUT_OF_MEMORY, "%s: out of device memory", fn);
-  const size_t o_out = (size_t)inst * sizeof(rg_desc), bytes = o_out + (size_t)inst * 8;
-  uint8_t* h = staging_begin(c, bytes);
-  if (!h) return fail(c, HBX_E_OUT_OF_MEMORY, "%s: descriptor staging", fn);
-  rg_fill(reinterpret_cast<rg_desc*>(h), off, len, pitch, inst);
-  memcpy(h + o_out, out_off, (size_t)inst * 8);
-  rc = staging_upload(c, bytes, s);
+  staging st(c, {(size_t)inst * sizeof(rg_desc), (size_t)inst * 8});  // rg_desc[inst] | out_off u64[inst]
+  if (!st.pin) return fail(c, HBX_E_OUT_OF_MEMORY, "%s: descriptor staging", fn);
+  memcpy(st.host<uint64_t>(1), out_off, (size_t)inst * 8);
+  rc = rg_upload(st, off, len, pitch, inst, s);
   if (rc) return rc;
-  const rg_desc* d_desc = c->rg_dev.as<rg_desc>();
-  rc = rs_reconstruct_rg(c, d_buf, d_desc, max_len, d_present, inst, k, m, d_status, s);
+  rc = rs_reconstruct_rg(c, d_buf, st.dev<rg_desc>(0), max_len, d_present, inst, k, m, d_status, s);
   if (rc) return rc;
-  if (d_leaf_hash) {
-    const uint32_t words = inst * n * 8;
-    hipLaunchKernelGGL(k_import_leaf_hashes, dim3((words + 255) / 256), dim3(256), 0, s, d_leaf_hash, d_present,
-                       inst * n, c->leaf_hash.as<uint32_t>());
-    if (m)  // Coding::Trivial reconstructs nothing
-      hipLaunchKernelGGL(k_missing_slots, dim3(inst), dim3(64), 0, s, d_present, n, d_status, m,
-                         c->leaf_slots.as<uint16_t>());
-    HIPCHK(c, hipGetLastError());
-    rc = merkle_tree_rg(c, d_buf, d_desc, inst, n, c->leaf_slots.as<uint16_t>(), m, m != 0, c->roots.as<uint8_t>(),
-                        nullptr, s);
-  } else {
-    rc = merkle_tree_rg(c, d_buf, d_desc, inst, n, nullptr, 0, true, c->roots.as<uint8_t>(), nullptr, s);
-  }
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_root_check, dim3((inst + 63) / 64), dim3(64), 0, s, c->roots.as<uint8_t>(), d_root_expect, inst,
-                     d_status);
-  const uint64_t glue_blocks = ((uint64_t)k * max_len + 4095) / 4096;
-  hipLaunchKernelGGL(k_glue_rg, dim3((unsigned)glue_blocks, inst), dim3(256), 0, s, d_buf, d_desc, k, d_out,
-                     reinterpret_cast<const uint64_t*>(c->rg_dev.as<uint8_t>() + o_out), d_out_len, d_status);
-  HIPCHK(c, hipGetLastError());
-  return HBX_OK;
+  return decode_tail_rg(c, d_buf, st.dev<rg_desc>(0), max_len, d_present, d_leaf_hash, d_root_expect, inst, k, m, d_out,
+                        st.dev<uint64_t>(1), d_out_len, d_status, s);
 }
 
 // ---- Broadcast, host-pointer forms (include/hbx.h): the _d calls above on context-owned staging
@@ -1811,6 +1811,33 @@ static uint8_t* stage(hbx_ctx* c, int slot, size_t bytes) {
   if (!ptr) return fail(c, HBX_E_OUT_OF_MEMORY, "%s: out of device memory (staging)", what)
 #define HBX_H2D(dst, src, bytes) HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream))
 #define HBX_D2H(dst, src, bytes) HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream))
+
+// P proofs up into hs[1..4]: node hashes, sibling hashes, u = sides | depth (| `more` u32 columns), roots.
+struct proof_dev { uint8_t *nodes, *sibs, *root; uint32_t* u; };
+static int stage_proofs(hbx_ctx* c, const char* fn, size_t P, const uint8_t* node_hash, const uint8_t* sib_hash,
+                        const uint32_t* sides, const uint32_t* depth, const uint8_t* root, size_t more, proof_dev* pd) {
+  HBX_STAGE(dh, 1, P * 17 * 32, fn);
+  HBX_STAGE(dsib, 2, P * 16 * 32, fn);
+  HBX_STAGE(du, 3, P * 4 * (2 + more), fn);
+  HBX_STAGE(dr, 4, P * 32, fn);
+  HBX_H2D(dh, node_hash, P * 17 * 32);
+  HBX_H2D(dsib, sib_hash, P * 16 * 32);
+  HBX_H2D(du, sides, P * 4);
+  HBX_H2D(du + P * 4, depth, P * 4);
+  HBX_H2D(dr, root, P * 32);
+  *pd = proof_dev{dh, dsib, dr, (uint32_t*)du};
+  return HBX_OK;
+}
+
+// A decode's payload bytes and dlen = out_len u64[count] | status i32[count] back; synchronised at return.
+static int decode_readback(hbx_ctx* c, uint8_t* out, const uint8_t* dout, size_t out_bytes, uint64_t* out_len,
+                           int32_t* status, const uint8_t* dlen, size_t count) {
+  if (out_bytes) HBX_D2H(out, dout, out_bytes);
+  HBX_D2H(out_len, dlen, count * 8);
+  HBX_D2H(status, dlen + count * 8, count * 4);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return HBX_OK;
+}
 
 int hbx_rs_encode(hbx_ctx* c, uint8_t* shards, uint32_t inst, uint32_t k, uint32_t m, uint32_t L) {
   if (!c || !shards || inst == 0 || L == 0) return fail(c, HBX_E_INVALID_ARG, "hbx_rs_encode: bad args");
@@ -1921,21 +1948,14 @@ int hbx_merkle_validate(hbx_ctx* c, const uint8_t* values, uint32_t vlen, const 
   HBX_ENTER(c, c->stream);
   const size_t P = nproofs;
   HBX_STAGE(dv, 0, P * vlen, "hbx_merkle_validate");
-  HBX_STAGE(dh, 1, P * 17 * 32, "hbx_merkle_validate");
-  HBX_STAGE(dsib, 2, P * 16 * 32, "hbx_merkle_validate");
-  HBX_STAGE(du, 3, P * 12, "hbx_merkle_validate");  // sides | depth | sender
-  HBX_STAGE(dr, 4, P * 32, "hbx_merkle_validate");
   HBX_STAGE(dok, 5, P, "hbx_merkle_validate");
+  proof_dev pd;
+  if (int rc = stage_proofs(c, "hbx_merkle_validate", P, node_hash, sib_hash, sides, depth, root, 1, &pd)) return rc;
   HBX_H2D(dv, values, P * vlen);
-  HBX_H2D(dh, node_hash, P * 17 * 32);
-  HBX_H2D(dsib, sib_hash, P * 16 * 32);
-  HBX_H2D(du, sides, P * 4);
-  HBX_H2D(du + P * 4, depth, P * 4);
-  HBX_H2D(du + P * 8, sender, P * 4);
-  HBX_H2D(dr, root, P * 32);
-  const uint32_t* u = (const uint32_t*)du;
-  int rc = hbx_merkle_validate_d(c, dv, vlen, dh, dsib, u, u + P, dr, u + 2 * P, count, nproofs, dok, c->stream);
-  if (rc) return rc;
+  HBX_H2D(pd.u + 2 * P, sender, P * 4);  // the one more column of pd.u
+  if (int rc = hbx_merkle_validate_d(c, dv, vlen, pd.nodes, pd.sibs, pd.u, pd.u + P, pd.root, pd.u + 2 * P, count,
+                                     nproofs, dok, c->stream))
+    return rc;
   HBX_D2H(valid, dok, P);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return HBX_OK;
@@ -1968,11 +1988,7 @@ static int broadcast_decode_host(hbx_ctx* c, uint8_t* shards, const uint8_t* pre
                             (int32_t*)(dlen + (size_t)inst * 8), c->stream);
   if (rc) return rc;
   HBX_D2H(shards, d, all);
-  HBX_D2H(out, dout, (size_t)inst * out_stride);
-  HBX_D2H(out_len, dlen, (size_t)inst * 8);
-  HBX_D2H(status, dlen + (size_t)inst * 8, (size_t)inst * 4);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return HBX_OK;
+  return decode_readback(c, out, dout, (size_t)inst * out_stride, out_len, status, dlen, inst);
 }
 
 int hbx_broadcast_decode(hbx_ctx* c, uint8_t* shards, const uint8_t* present, const uint8_t* root_expect, uint32_t inst,
@@ -1994,8 +2010,7 @@ int hbx_prepare_broadcast(hbx_ctx* c, uint32_t inst, uint32_t k, uint32_t m, uin
   const char* fn = "hbx_prepare_broadcast";
   if (!c || inst == 0 || max_shard_len == 0 || max_shard_len > 0xFFFFFFF0u)
     return fail(c, HBX_E_INVALID_ARG, "%s: bad args", fn);
-  if (k == 0 || k > (uint32_t)RS_MAX_K || k + m > (uint32_t)RS_MAX_N)
-    return fail(c, HBX_E_INVALID_ARG, "rs: need 1 <= k <= %d and k + m <= %d (k=%u m=%u)", RS_MAX_K, RS_MAX_N, k, m);
+  if (int rc = rs_bounds(c, k, m)) return rc;
   HBX_ENTER(c, c->stream);
   const size_t slots = (size_t)inst * (k + m);
   const uint32_t pitch = (max_shard_len + 3) & ~3u;
@@ -2015,23 +2030,10 @@ int hbx_prepare_broadcast(hbx_ctx* c, uint32_t inst, uint32_t k, uint32_t m, uin
   return HBX_OK;
 }
 
-static int bc_plan_rejected(hbx_ctx* c, int rc, const char* fn) {
-  switch (rc) {
-    case hbx_bcplan::PLAN_BAD_INST:
-      return fail(c, HBX_E_INVALID_ARG, "%s: an instance is not below the store's %u", fn, c->bc_inst);
-    case hbx_bcplan::PLAN_BAD_SENDER:
-      return fail(c, HBX_E_INVALID_ARG, "%s: a sender is not below n = %u", fn, c->bc_k + c->bc_m);
-    case hbx_bcplan::PLAN_DUPLICATE:
-      return fail(c, HBX_E_INVALID_ARG, "%s: the same entry twice in one call", fn);
-    case hbx_bcplan::PLAN_BAD_OFFSETS:
-      return fail(c, HBX_E_INVALID_ARG, "%s: val_off is not a non-decreasing offset list within the values", fn);
-    case hbx_bcplan::PLAN_BAD_LEN:
-      return fail(c, HBX_E_INVALID_ARG, "%s: need 1 <= len <= max_shard_len = %u", fn, c->bc_max);
-    case hbx_bcplan::PLAN_NO_ROOM:
-      return fail(c, HBX_E_INVALID_ARG, "%s: an attempt has no room of its own for k len - 4 output bytes", fn);
-    default:
-      return HBX_OK;
-  }
+static int bc_enter(hbx_ctx* c, const char* fn) {
+  if (!c) return HBX_E_INVALID_ARG;
+  if (!c->bc_live) return fail(c, HBX_E_NO_BROADCAST, "%s: no echo store (hbx_prepare_broadcast)", fn);
+  return HBX_OK;
 }
 
 int hbx_add_echoes_d(hbx_ctx* c, const uint8_t* d_values, uint64_t values_bytes, const uint64_t* val_off,
@@ -2039,8 +2041,7 @@ int hbx_add_echoes_d(hbx_ctx* c, const uint8_t* d_values, uint64_t values_bytes,
                      const uint32_t* d_depth, const uint8_t* d_root, const uint32_t* inst, const uint32_t* sender,
                      uint32_t count, uint8_t* d_status, void* stream) {
   const char* fn = "hbx_add_echoes_d";
-  if (!c) return HBX_E_INVALID_ARG;
-  if (!c->bc_live) return fail(c, HBX_E_NO_BROADCAST, "%s: no echo store (hbx_prepare_broadcast)", fn);
+  if (int rc = bc_enter(c, fn)) return rc;
   if (count == 0) return HBX_OK;
   if (!d_values || !val_off || !d_node_hash || !d_sib_hash || !d_sides || !d_depth || !d_root || !inst || !sender)
     return fail(c, HBX_E_INVALID_ARG, "%s: bad args", fn);
@@ -2048,45 +2049,24 @@ int hbx_add_echoes_d(hbx_ctx* c, const uint8_t* d_values, uint64_t values_bytes,
   if (int rc = hbx_bcplan::check_items(inst, sender, count, n, c->bc_inst)) return bc_plan_rejected(c, rc, fn);
   if (int rc = hbx_bcplan::check_offsets(val_off, count, values_bytes)) return bc_plan_rejected(c, rc, fn);
   HBX_ENTER(c, stream);
-  const uint32_t B = c->merkle == HBX_MERKLE_SHA256 ? 64 : 32;
-  std::vector<uint32_t> blk_len, blk_idx;
-  hbx_bcplan::group_long(val_off, count, B, (uint64_t)c->bc_max + 1, blk_len, blk_idx);
-  const size_t nblk = blk_len.size();
-  // staging: val_off u64[count + 1] | items uint2[count] | sender u32[count] | blk_len | blk_idx
-  const size_t o_items = (size_t)(count + 1) * 8, o_snd = o_items + (size_t)count * 8,
-               o_len = (o_snd + (size_t)count * 4 + 7) & ~(size_t)7, o_idx = o_len + ((nblk * 4 + 7) & ~(size_t)7),
-               bytes = o_idx + nblk * B * 4;
-  uint8_t* h = staging_begin(c, bytes);
-  if (!h || (nblk && !c->val_digest.ensure((size_t)count * 32)) || (!d_status && !c->bc_item_st.ensure(count)))
+  const long_values lv(c, val_off, count, (uint64_t)c->bc_max + 1);
+  // staging after the long values' ranges: items uint2[count] | sender u32[count]
+  const staging stg = lv.stage(c, val_off, count, (size_t)count * 8, (size_t)count * 4);
+  if (!stg.pin || (lv.blocks() && !c->val_digest.ensure((size_t)count * 32)) ||
+      (!d_status && !c->bc_item_st.ensure(count)))
     return fail(c, HBX_E_OUT_OF_MEMORY, "%s: out of memory", fn);
-  memcpy(h, val_off, o_items);
-  uint2* it = reinterpret_cast<uint2*>(h + o_items);
+  uint2* it = stg.host<uint2>(3);
   for (uint32_t j = 0; j < count; j++) it[j] = make_uint2(inst[j], sender[j]);
-  memcpy(h + o_snd, sender, (size_t)count * 4);
-  if (nblk) {
-    memcpy(h + o_len, blk_len.data(), nblk * 4);
-    memcpy(h + o_idx, blk_idx.data(), nblk * B * 4);
-  }
-  if (int rc = staging_upload(c, bytes, s)) return rc;
-  const uint8_t* dv = c->rg_dev.as<uint8_t>();
-  const uint64_t* d_off = reinterpret_cast<const uint64_t*>(dv);
-  const uint2* d_items = reinterpret_cast<const uint2*>(dv + o_items);
+  memcpy(stg.host<uint32_t>(4), sender, (size_t)count * 4);
+  if (int rc = stg.upload(s)) return rc;
+  const uint64_t* d_off = stg.dev<uint64_t>(0);
+  const uint2* d_items = stg.dev<uint2>(3);
   uint8_t* st = d_status ? d_status : c->bc_item_st.as<uint8_t>();
   hipLaunchKernelGGL(k_echo_precheck, dim3((count + 63) / 64), dim3(64), 0, s, d_items, d_off, count, n, c->bc_max,
                      c->bc_state.as<uint8_t>(), st);
-  if (nblk) {
-    timed t_(c, HBX_K_MERKLE_LEAVES, s);
-    if (c->merkle == HBX_MERKLE_SHA256)
-      hipLaunchKernelGGL(k_echo_values_sha256, dim3((unsigned)nblk), dim3(128), 0, s, d_values, d_off,
-                         reinterpret_cast<const uint32_t*>(dv + o_len), reinterpret_cast<const uint32_t*>(dv + o_idx), st,
-                         c->val_digest.as<uint32_t>());
-    else
-      hipLaunchKernelGGL(k_echo_values_sha3, dim3((unsigned)nblk), dim3(64), 0, s, d_values, d_off,
-                         reinterpret_cast<const uint32_t*>(dv + o_len), reinterpret_cast<const uint32_t*>(dv + o_idx), st,
-                         c->val_digest.as<uint32_t>());
-  }
+  lv.hash(c, s, stg, k_echo_values_sha256, k_echo_values_sha3, d_values, st, c->val_digest.as<uint32_t>());
   hipLaunchKernelGGL(k_echo_validate, dim3((count + 63) / 64), dim3(64), 0, s, d_values, d_off, d_node_hash, d_sib_hash,
-                     d_sides, d_depth, d_root, reinterpret_cast<const uint32_t*>(dv + o_snd), n, count, st, c->merkle,
+                     d_sides, d_depth, d_root, stg.dev<uint32_t>(4), n, count, st, c->merkle,
                      c->val_digest.as<uint32_t>());
   // the longest value that can be stored bounds the copy grid; shorter items' spare blocks return at once
   uint64_t longest = 0;
@@ -2111,8 +2091,7 @@ int hbx_add_echoes(hbx_ctx* c, const uint8_t* values, uint64_t values_bytes, con
                    const uint8_t* node_hash, const uint8_t* sib_hash, const uint32_t* sides, const uint32_t* depth,
                    const uint8_t* root, const uint32_t* inst, const uint32_t* sender, uint32_t count, uint8_t* status) {
   const char* fn = "hbx_add_echoes";
-  if (!c) return HBX_E_INVALID_ARG;
-  if (!c->bc_live) return fail(c, HBX_E_NO_BROADCAST, "%s: no echo store (hbx_prepare_broadcast)", fn);
+  if (int rc = bc_enter(c, fn)) return rc;
   if (count == 0) return HBX_OK;
   if (!values || !val_off || !node_hash || !sib_hash || !sides || !depth || !root || !inst || !sender)
     return fail(c, HBX_E_INVALID_ARG, "%s: bad args", fn);
@@ -2120,19 +2099,12 @@ int hbx_add_echoes(hbx_ctx* c, const uint8_t* values, uint64_t values_bytes, con
   HBX_ENTER(c, c->stream);
   const size_t P = count;
   HBX_STAGE(dv, 0, values_bytes, fn);
-  HBX_STAGE(dh, 1, P * 17 * 32, fn);
-  HBX_STAGE(dsib, 2, P * 16 * 32, fn);
-  HBX_STAGE(du, 3, P * 8, fn);  // sides | depth
-  HBX_STAGE(dr, 4, P * 32, fn);
   HBX_STAGE(dst, 5, P, fn);
+  proof_dev pd;
+  if (int rc = stage_proofs(c, fn, P, node_hash, sib_hash, sides, depth, root, 0, &pd)) return rc;
   if (values_bytes) HBX_H2D(dv, values, values_bytes);
-  HBX_H2D(dh, node_hash, P * 17 * 32);
-  HBX_H2D(dsib, sib_hash, P * 16 * 32);
-  HBX_H2D(du, sides, P * 4);
-  HBX_H2D(du + P * 4, depth, P * 4);
-  HBX_H2D(dr, root, P * 32);
-  const uint32_t* u = (const uint32_t*)du;
-  if (int rc = hbx_add_echoes_d(c, dv, values_bytes, val_off, dh, dsib, u, u + P, dr, inst, sender, count, dst, c->stream))
+  if (int rc = hbx_add_echoes_d(c, dv, values_bytes, val_off, pd.nodes, pd.sibs, pd.u, pd.u + P, pd.root, inst, sender,
+                                count, dst, c->stream))
     return rc;
   std::vector<uint8_t> got(P);
   HBX_D2H(got.data(), dst, P);
@@ -2145,8 +2117,7 @@ int hbx_broadcast_decode_insts_d(hbx_ctx* c, const uint32_t* insts, const uint8_
                                  const uint8_t* use, uint32_t na, uint8_t* d_out, uint64_t out_bytes,
                                  const uint64_t* out_off, uint64_t* d_out_len, int32_t* d_status, void* stream) {
   const char* fn = "hbx_broadcast_decode_insts_d";
-  if (!c) return HBX_E_INVALID_ARG;
-  if (!c->bc_live) return fail(c, HBX_E_NO_BROADCAST, "%s: no echo store (hbx_prepare_broadcast)", fn);
+  if (int rc = bc_enter(c, fn)) return rc;
   if (na == 0) return HBX_OK;
   if (!insts || !roots || !len || (!d_out && out_bytes) || !out_off || !d_out_len || !d_status)
     return fail(c, HBX_E_INVALID_ARG, "%s: bad args", fn);
@@ -2165,30 +2136,26 @@ int hbx_broadcast_decode_insts_d(hbx_ctx* c, const uint32_t* insts, const uint8_
   if (rc) return rc;
   const size_t cells = (size_t)na * n;
   if (!c->bc_work.ensure(work_bytes) || !c->bc_present.ensure(cells) || !c->bc_leaf_w.ensure(cells * 32) ||
-      !c->bc_size_bad.ensure((size_t)na * 4) || !c->roots.ensure((size_t)na * 32) || !c->leaf_hash.ensure(cells * 32) ||
-      !c->leaf_slots.ensure((size_t)na * (m ? m : 1) * 2))
+      !c->bc_size_bad.ensure((size_t)na * 4))
     return fail(c, HBX_E_OUT_OF_MEMORY, "%s: out of device memory", fn);
   // staging: rg_desc[na] | out_off u64[na] | insts u32[na] | roots [na][32] | use [na][n]
-  const size_t o_out = (size_t)na * sizeof(rg_desc), o_inst = o_out + (size_t)na * 8, o_root = o_inst + (size_t)na * 4,
-               o_use = o_root + (size_t)na * 32, bytes = o_use + cells;
-  uint8_t* h = staging_begin(c, bytes);
-  if (!h) return fail(c, HBX_E_OUT_OF_MEMORY, "%s: descriptor staging", fn);
-  rg_fill(reinterpret_cast<rg_desc*>(h), off.data(), len, pitch.data(), na);
-  memcpy(h + o_out, out_off, (size_t)na * 8);
-  memcpy(h + o_inst, insts, (size_t)na * 4);
-  memcpy(h + o_root, roots, (size_t)na * 32);
-  if (use) memcpy(h + o_use, use, cells);
-  else memset(h + o_use, 1, cells);
-  rc = staging_upload(c, bytes, s);
+  staging st(c, {(size_t)na * sizeof(rg_desc), (size_t)na * 8, (size_t)na * 4, (size_t)na * 32, cells});
+  if (!st.pin) return fail(c, HBX_E_OUT_OF_MEMORY, "%s: descriptor staging", fn);
+  memcpy(st.host<uint64_t>(1), out_off, (size_t)na * 8);
+  memcpy(st.host<uint32_t>(2), insts, (size_t)na * 4);
+  memcpy(st.host<uint8_t>(3), roots, (size_t)na * 32);
+  if (use) memcpy(st.host<uint8_t>(4), use, cells);
+  else memset(st.host<uint8_t>(4), 1, cells);
+  rc = rg_upload(st, off.data(), len, pitch.data(), na, s);
   if (rc) return rc;
-  const uint8_t* dv = c->rg_dev.as<uint8_t>();
-  const rg_desc* d_desc = c->rg_dev.as<rg_desc>();
+  const rg_desc* d_desc = st.dev<rg_desc>(0);
+  const uint8_t* d_roots = st.dev<uint8_t>(3);
   uint8_t* work = c->bc_work.as<uint8_t>();
   const uint8_t* d_present = c->bc_present.as<uint8_t>();
   HIPCHK(c, hipMemsetAsync(c->bc_size_bad.p, 0, (size_t)na * 4, s));
   const uint32_t per_block = 256 * ECHO_COPY;
   hipLaunchKernelGGL(k_echo_gather, dim3((max_len + per_block - 1) / per_block, n, na), dim3(256), 0, s,
-                     reinterpret_cast<const uint32_t*>(dv + o_inst), dv + o_root, dv + o_use, d_desc, n, c->bc_pitch,
+                     st.dev<uint32_t>(2), d_roots, st.dev<uint8_t>(4), d_desc, n, c->bc_pitch,
                      c->bc_shard.as<uint8_t>(), c->bc_len.as<uint32_t>(), c->bc_root.as<uint8_t>(),
                      c->bc_leaf.as<uint8_t>(), c->bc_state.as<uint8_t>(), work, c->bc_present.as<uint8_t>(),
                      c->bc_leaf_w.as<uint8_t>(), c->bc_size_bad.as<uint32_t>());
@@ -2198,27 +2165,15 @@ int hbx_broadcast_decode_insts_d(hbx_ctx* c, const uint32_t* insts, const uint8_
   if (rc) return rc;
   hipLaunchKernelGGL(k_echo_size_status, dim3((na + 63) / 64), dim3(64), 0, s, c->bc_size_bad.as<uint32_t>(), na,
                      (int32_t)HBX_E_SHARD_SIZE, d_status);
-  hipLaunchKernelGGL(k_import_leaf_hashes, dim3(((uint32_t)cells * 8 + 255) / 256), dim3(256), 0, s,
-                     c->bc_leaf_w.as<uint8_t>(), d_present, (uint32_t)cells, c->leaf_hash.as<uint32_t>());
-  if (m)
-    hipLaunchKernelGGL(k_missing_slots, dim3(na), dim3(64), 0, s, d_present, n, d_status, m, c->leaf_slots.as<uint16_t>());
-  HIPCHK(c, hipGetLastError());
-  rc = merkle_tree_rg(c, work, d_desc, na, n, c->leaf_slots.as<uint16_t>(), m, m != 0, c->roots.as<uint8_t>(), nullptr, s);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_root_check, dim3((na + 63) / 64), dim3(64), 0, s, c->roots.as<uint8_t>(), dv + o_root, na, d_status);
-  const uint64_t glue_blocks = ((uint64_t)k * max_len + 4095) / 4096;
-  hipLaunchKernelGGL(k_glue_rg, dim3((unsigned)glue_blocks, na), dim3(256), 0, s, work, d_desc, k, d_out,
-                     reinterpret_cast<const uint64_t*>(dv + o_out), d_out_len, d_status);
-  HIPCHK(c, hipGetLastError());
-  return HBX_OK;
+  return decode_tail_rg(c, work, d_desc, max_len, d_present, c->bc_leaf_w.as<uint8_t>(), d_roots, na, k, m, d_out,
+                        st.dev<uint64_t>(1), d_out_len, d_status, s);
 }
 
 int hbx_broadcast_decode_insts(hbx_ctx* c, const uint32_t* insts, const uint8_t* roots, const uint32_t* len,
                                const uint8_t* use, uint32_t na, uint8_t* out, uint64_t out_bytes, const uint64_t* out_off,
                                uint64_t* out_len, int32_t* status) {
   const char* fn = "hbx_broadcast_decode_insts";
-  if (!c) return HBX_E_INVALID_ARG;
-  if (!c->bc_live) return fail(c, HBX_E_NO_BROADCAST, "%s: no echo store (hbx_prepare_broadcast)", fn);
+  if (int rc = bc_enter(c, fn)) return rc;
   if (na == 0) return HBX_OK;
   if ((!out && out_bytes) || !out_len || !status) return fail(c, HBX_E_INVALID_ARG, "%s: bad args", fn);
   HBX_ENTER(c, c->stream);
@@ -2228,17 +2183,11 @@ int hbx_broadcast_decode_insts(hbx_ctx* c, const uint32_t* insts, const uint8_t*
   if (int rc = hbx_broadcast_decode_insts_d(c, insts, roots, len, use, na, dout, out_bytes, out_off, (uint64_t*)dlen,
                                             (int32_t*)(dlen + (size_t)na * 8), c->stream))
     return rc;
-  if (out_bytes) HBX_D2H(out, dout, out_bytes);
-  HBX_D2H(out_len, dlen, (size_t)na * 8);
-  HBX_D2H(status, dlen + (size_t)na * 8, (size_t)na * 4);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return HBX_OK;
+  return decode_readback(c, out, dout, out_bytes, out_len, status, dlen, na);
 }
 
 int hbx_get_echo_slots(hbx_ctx* c, uint8_t* state, uint32_t* len, uint8_t* root) {
-  const char* fn = "hbx_get_echo_slots";
-  if (!c) return HBX_E_INVALID_ARG;
-  if (!c->bc_live) return fail(c, HBX_E_NO_BROADCAST, "%s: no echo store (hbx_prepare_broadcast)", fn);
+  if (int rc = bc_enter(c, "hbx_get_echo_slots")) return rc;
   HBX_ENTER(c, c->stream);
   const size_t slots = (size_t)c->bc_inst * (c->bc_k + c->bc_m);
   if (state) HBX_D2H(state, c->bc_state.p, slots);
@@ -2874,11 +2823,11 @@ int hbx_combine_signatures_insts_d(hbx_ctx* c, const uint8_t* master_pk48, uint3
   if (ninsts == 0) return HBX_OK;
   HBX_ENTER(c, stream);
   // the listed instances, consumed before the call returns (pinned staging, as an add's items)
-  uint8_t* pin = staging_begin(c, (size_t)ninsts * 4);
-  if (!pin) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_combine_signatures_insts_d: out of memory (staging)");
-  memcpy(pin, insts, (size_t)ninsts * 4);
-  if (int rc = staging_upload(c, (size_t)ninsts * 4, s)) return rc;
-  const uint32_t* d_insts = c->rg_dev.as<uint32_t>();
+  const staging st(c, {(size_t)ninsts * 4});
+  if (!st.pin) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_combine_signatures_insts_d: out of memory (staging)");
+  memcpy(st.pin, insts, (size_t)ninsts * 4);
+  if (int rc = st.upload(s)) return rc;
+  const uint32_t* d_insts = st.dev<uint32_t>(0);
   if (int rc = combine_sigs_impl(c, master_pk48, t, d_use, s, d_insts, ninsts)) return rc;
   if (d_sig96 || d_status || d_master_ok || d_parity) {
     hipLaunchKernelGGL(k_coin_scatter, dim3((ninsts * 96 + 255) / 256), dim3(256), 0, s, d_insts, ninsts,
@@ -2948,11 +2897,11 @@ static int combine_impl(hbx_ctx* c, uint32_t t, uint8_t* d_out_blob, int32_t* d_
   const uint32_t* d_cols = nullptr;
   const uint32_t pl = cols ? ncols : p;  // proposers of this launch
   if (cols) {
-    uint8_t* pin = staging_begin(c, (size_t)ncols * 4);
-    if (!pin) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_combine_decrypt_cols_d: out of memory (staging)");
-    memcpy(pin, cols, (size_t)ncols * 4);
-    if (int rc = staging_upload(c, (size_t)ncols * 4, s)) return rc;
-    d_cols = c->rg_dev.as<uint32_t>();
+    const staging st(c, {(size_t)ncols * 4});
+    if (!st.pin) return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_combine_decrypt_cols_d: out of memory (staging)");
+    memcpy(st.pin, cols, (size_t)ncols * 4);
+    if (int rc = st.upload(s)) return rc;
+    d_cols = st.dev<uint32_t>(0);
   }
   if (!c->keys.ensure((size_t)p * 32) || !c->status.ensure((size_t)p * 4))
     return fail(c, HBX_E_OUT_OF_MEMORY, "hbx_combine_decrypt_d: out of device memory");

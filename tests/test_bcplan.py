@@ -1,7 +1,7 @@
 """The host planner of hbx_add_echoes_d / hbx_broadcast_decode_insts_d (hbbft_amd/csrc/bcplan.hpp),
 compiled for the CPU by g++ (tools/hostcheck/bcplancheck.cpp) and compared with a Python model: the
-duplicate and bounds checks, the offset list, the grouping of long values into hash blocks and the
-work-buffer layout of a decode list.  The same source builds as a stand-alone program with
+duplicate and bounds checks, the offset list, the grouping of long values into hash blocks, the
+work-buffer layout of a decode list, and the row descriptors of the ragged calls.  The same source builds as a stand-alone program with
 -fsanitize=address,undefined, which plans the same edge sets in a subprocess (nothing sanitized is
 loaded into Python)."""
 import ctypes
@@ -26,11 +26,14 @@ def bp(tmp_path_factory):
     P, u32, u64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
     lib.bp_check_items.argtypes = [P, P, u32, u32, u32]
     lib.bp_check_offsets.argtypes = [P, u32, u64]
+    lib.bp_check_offsets_bad.argtypes = [P, u32, u64, P]
+    lib.bp_check_rows.argtypes = [u64, P, P, P, u32, u32, P, P]
     lib.bp_group_long.argtypes = [P, u32, u32, u64, P, P, u32]
     lib.bp_check_attempts.argtypes = [P, P, P, P, u32, u32, u32, u32]
     lib.bp_work_layout.argtypes = [P, u32, u32, P, P]
     lib.bp_work_layout.restype = u64
     lib.bp_check_out.argtypes = [P, P, u32, u32, u64]
+    lib.bp_check_out_bad.argtypes = [P, P, u32, u32, u64, P]
     return lib
 
 
@@ -56,6 +59,54 @@ def model_offsets(off, nbytes):
     if any(b < a or b - a > 0xFFFFFFFF for a, b in zip(off[:-1], off[1:])):
         return BAD_OFFSETS
     return BAD_OFFSETS if off[-1] > nbytes else OK
+
+
+def model_offsets_bad(off):
+    """The first j whose off[j..j + 1] is no value; the count for a list that is one."""
+    return next((j for j, (a, b) in enumerate(zip(off[:-1], off[1:])) if b < a or b - a > 0xFFFFFFFF), len(off) - 1)
+
+
+ROWS_OK, ROWS_UNALIGNED, ROWS_BAD_LEN, ROWS_PAST_END, ROWS_OVERLAP = range(5)
+
+
+def model_rows(buf_bytes, rows, n):
+    """rows: (off, len, pitch) per instance -> (code, offending instances, longest shard)."""
+    for q, (o, v, p) in enumerate(rows):
+        if o % 4 or p % 4:
+            return ROWS_UNALIGNED, [q], None
+        if v == 0 or p < v:
+            return ROWS_BAD_LEN, [q], None
+        if o > buf_bytes or n * p > buf_bytes - o:
+            return ROWS_PAST_END, [q], None
+    order = sorted(range(len(rows)), key=lambda q: rows[q][0])
+    for a, b in zip(order[:-1], order[1:]):
+        if rows[b][0] < rows[a][0] + n * rows[a][2]:
+            return ROWS_OVERLAP, [a, b], None
+    return ROWS_OK, [], max(v for _, v, _ in rows)
+
+
+def rows_check(bp, buf_bytes, rows, n):
+    off, v, p = _u64(r[0] for r in rows), _u32(r[1] for r in rows), _u32(r[2] for r in rows)
+    mx, bad = np.zeros(1, dtype=np.uint32), np.zeros(2, dtype=np.uint32)
+    rc = bp.bp_check_rows(buf_bytes, off.ctypes.data, v.ctypes.data, p.ctypes.data, len(rows), n, mx.ctypes.data,
+                          bad.ctypes.data)
+    return rc, [int(x) for x in bad[:{ROWS_OK: 0, ROWS_OVERLAP: 2}.get(rc, 1)]], int(mx[0]) if rc == ROWS_OK else None
+
+
+TOP = 1 << 64
+ROW_SETS = [  # (name, n, buf_bytes, [(off, len, pitch)])
+    ("one", 4, 64, [(0, 5, 8)]), ("off not a multiple of 4", 4, 64, [(2, 5, 8)]),
+    ("pitch not a multiple of 4", 4, 64, [(0, 5, 6)]), ("len 0", 4, 64, [(0, 0, 8)]), ("pitch < len", 4, 64, [(0, 9, 8)]),
+    ("ends at the buffer", 4, 64, [(32, 8, 8)]), ("one byte past", 4, 63, [(32, 8, 8)]),
+    ("pitch rounds the last row past", 4, 62, [(32, 5, 8)]), ("off past the buffer", 4, 64, [(68, 4, 4)]),
+    ("off at the buffer", 4, 64, [(64, 4, 4)]), ("two that touch", 4, 64, [(32, 5, 8), (0, 8, 8)]),
+    ("overlap by one row", 4, 64, [(24, 5, 8), (0, 8, 8)]), ("same offset", 2, 64, [(8, 4, 4), (8, 4, 4)]),
+    ("second instance wins its own rule", 4, 64, [(0, 5, 8), (32, 9, 8)]),
+    ("three, the middle pair", 2, 96, [(64, 8, 8), (0, 8, 8), (12, 8, 8)]),
+    ("near 2^64", 256, TOP - 1, [(TOP - 1024, 4, 4)]), ("near 2^64, one row past", 256, TOP - 1, [(TOP - 1020, 4, 4)]),
+    ("off near 2^64, past the buffer", 256, 1 << 40, [(TOP - 4, 4, 4)]),
+    ("wide pitch", 256, TOP - 1, [(0, 4, 0xFFFFFFFC), (256 * 0xFFFFFFFC, 0xFFFFFFFC, 0xFFFFFFFC)]),
+]
 
 
 def model_groups(lens, lanes, max_value):
@@ -102,6 +153,12 @@ def model_out(lens, out_off, k, out_bytes):
             rng.append((o, o + need))
     rng.sort()
     return NO_ROOM if any(b[0] < a[1] for a, b in zip(rng[:-1], rng[1:])) else OK
+
+
+def model_out_bad(lens, out_off, k, out_bytes):
+    """The first attempt without room; the count when every attempt has room (ranges may still overlap)."""
+    return next((a for a, (v, o) in enumerate(zip(lens, out_off))
+                 if o > out_bytes or max(k * v - 4, 0) > out_bytes - o), len(lens))
 
 
 # ---- the planner through ctypes --------------------------------------------------------------
@@ -163,9 +220,56 @@ def test_items_random(bp):
 
 def test_offsets(bp):
     for off, nbytes in [([0], 0), ([0, 0, 0], 0), ([0, 5, 9], 9), ([0, 5, 9], 8), ([0, 5, 4], 9), ([3, 3, 10], 10),
-                        ([0, 1 << 32], 1 << 33), ([0, (1 << 32) - 1], 1 << 33), ([5, 2], 10)]:
-        o = _u64(off)
+                        ([0, 1 << 32], 1 << 33), ([0, (1 << 32) - 1], 1 << 33), ([5, 2], 10),
+                        ([0, 4, TOP - 1], TOP - 1), ([TOP - 8, TOP - 1], TOP - 2), ([0, 1, 1, 0, 9], 9)]:
+        o, bad = _u64(off), np.full(1, 77, dtype=np.uint32)
         assert bp.bp_check_offsets(o.ctypes.data, len(off) - 1, nbytes) == model_offsets(off, nbytes), off
+        assert bp.bp_check_offsets_bad(o.ctypes.data, len(off) - 1, nbytes, None) == model_offsets(off, nbytes), off
+        assert bp.bp_check_offsets_bad(o.ctypes.data, len(off) - 1, nbytes, bad.ctypes.data) == model_offsets(off, nbytes), off
+        assert int(bad[0]) == model_offsets_bad(off), off  # the pair a text names; the count: the list ends past the blob
+
+
+@pytest.mark.parametrize("name,n,buf_bytes,rows", ROW_SETS, ids=[s[0] for s in ROW_SETS])
+def test_rows(bp, name, n, buf_bytes, rows):
+    want = model_rows(buf_bytes, rows, n)
+    got = rows_check(bp, buf_bytes, rows, n)
+    if name == "same offset":  # the order of equal offsets is the sort's
+        got, want = (got[0], sorted(got[1]), got[2]), (want[0], sorted(want[1]), want[2])
+    assert got == want
+
+
+def test_rows_random(bp):
+    """Distinct offsets (a tie's order is the sort's): instances laid out back to back, then one rule broken."""
+    rnd = random.Random(13)
+    seen = set()
+    for _ in range(400):
+        n, inst = rnd.choice([1, 4, 7, 256]), rnd.choice([1, 2, 3, 9])
+        rows, at = [], 4 * rnd.randrange(3)
+        for _ in range(inst):
+            v = rnd.choice([1, 3, 4, 5, 300])
+            p = (v + 3) // 4 * 4 + 4 * rnd.randrange(2)
+            rows.append((at, v, p))
+            at += n * p + 4 * rnd.randrange(2)
+        buf_bytes = at + rnd.choice([0, 0, 1, 8])
+        q, how = rnd.randrange(inst), rnd.randrange(8)
+        o, v, p = rows[q]
+        if how == 0:
+            rows[q] = (o + 2, v, p)
+        elif how == 1:
+            rows[q] = (o, v, p + 2)
+        elif how == 2:
+            rows[q] = (o, rnd.choice([0, p + 1]), p)
+        elif how == 3:
+            buf_bytes = rows[-1][0] + n * rows[-1][2] - rnd.choice([1, 4])
+        elif how == 4 and q:
+            rows[q] = (o - 4 * rnd.randrange(1, 3), v, p)
+        rnd.shuffle(rows)
+        if len({r[0] for r in rows}) != len(rows):
+            continue
+        want = model_rows(buf_bytes, rows, n)
+        assert rows_check(bp, buf_bytes, rows, n) == want, (buf_bytes, rows, n)
+        seen.add(want[0])
+    assert seen == {ROWS_OK, ROWS_UNALIGNED, ROWS_BAD_LEN, ROWS_PAST_END, ROWS_OVERLAP}
 
 
 @pytest.mark.parametrize("name,lanes,max_value,lens", LEN_SETS, ids=[s[0] for s in LEN_SETS])
@@ -226,9 +330,13 @@ def test_attempts_without_use(bp):
 def test_output_room(bp):
     for lens, out_off, k, ob in [([10, 10], [0, 36], 4, 72), ([10, 10], [0, 35], 4, 72), ([10, 10], [0, 36], 4, 71),
                                  ([1], [0], 3, 0), ([1], [1], 3, 0), ([2], [0], 3, 2), ([2], [0], 3, 1), ([], [], 3, 0),
-                                 ([10, 1, 10], [0, 0, 40], 4, 76)]:
-        v, o = _u32(lens), _u64(out_off)
+                                 ([10, 1, 10], [0, 0, 40], 4, 76), ([10, 10, 10], [0, 36, 200], 4, 108),
+                                 ([4], [TOP - 13], 4, TOP - 1), ([4], [TOP - 12], 4, TOP - 1), ([4], [TOP - 1], 4, 8)]:
+        v, o, bad = _u32(lens), _u64(out_off), np.full(1, 77, dtype=np.uint32)
         assert bp.bp_check_out(v.ctypes.data, o.ctypes.data, len(lens), k, ob) == model_out(lens, out_off, k, ob), (lens, out_off)
+        assert bp.bp_check_out_bad(v.ctypes.data, o.ctypes.data, len(lens), k, ob, None) == model_out(lens, out_off, k, ob)
+        assert bp.bp_check_out_bad(v.ctypes.data, o.ctypes.data, len(lens), k, ob, bad.ctypes.data) == model_out(lens, out_off, k, ob)
+        assert int(bad[0]) == model_out_bad(lens, out_off, k, ob), (lens, out_off)
 
 
 def test_sanitized_program_plans_the_edge_sets(tmp_path):
@@ -257,6 +365,8 @@ def test_sanitized_program_plans_the_edge_sets(tmp_path):
             room.append(room[-1] + max(k * v - 4, 0))
         text += f"dec {n} {insts} {max_len} {k} {room[-1]} {len(att)} " + \
             " ".join(f"{q} {r} {v} {u} {o}" for (q, r, v, u), o in zip(att, room)) + "\n"
+    for _, n, buf_bytes, rows in ROW_SETS:
+        text += f"row {n} {buf_bytes} {len(rows)} " + " ".join(f"{o} {v} {p}" for o, v, p in rows) + "\n"
     run = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=120)
     assert run.returncode == 0, run.stderr
     assert run.stderr == ""
@@ -281,4 +391,11 @@ def test_sanitized_program_plans_the_edge_sets(tmp_path):
         assert head == ["total", str(total)]
         for o, p in zip(off, pitch):
             assert next(lines).split() == ["off", str(o), "pitch", str(p)]
+    for name, n, buf_bytes, rows in ROW_SETS:
+        code, bad, mx = model_rows(buf_bytes, rows, n)
+        head = [int(x) for x in next(lines).split()[1:]]
+        if code == ROWS_OK:
+            assert head == [mx]
+        else:
+            assert head[0] == code and (sorted(head[1:]) if name == "same offset" else head[1:1 + len(bad)]) == bad
     assert next(lines, None) is None

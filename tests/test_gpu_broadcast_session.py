@@ -444,3 +444,132 @@ def _raw(items, sender=None, val_off=None):
     _raw.keep = keep  # the arrays outlive the call
     return (blob.ctypes.data, blob.size, off.ctypes.data, nh.ctypes.data, sh.ctypes.data, sides.ctypes.data,
             depth.ctypes.data, root.ctypes.data, inst.ctypes.data, keep[-1].ctypes.data, len(items), None)
+
+
+# ---- the three decode forms share one tail --------------------------------------------------------
+FORM_LENS = [1, 5, 8]  # a payload too short for its header; L % 4 != 0 (the uniform byte kernel); dword rows
+FORM_PATTERNS = ["all present", "one data shard missing", "k - 1 present", "tampered tree", "wrong root"]
+
+
+def _form_cases(k, m, variant):
+    """Per shard length and pattern: (shards uint8[n, L], present [n], expected root, leaves or None
+    where the store cannot hold the case).  'tampered tree': the tree is built over shard 0 with a
+    flipped byte and shard 0 is withheld, so the rebuilt shard 0 misses the root (m == 0 rebuilds
+    nothing: too few shards).  'wrong root': all present under a root with a flipped byte, which no
+    stored proof can carry, so the store form leaves it out."""
+    n, rng, cases = k + m, random.Random(1000 * k + m), []
+    for L in FORM_LENS:
+        if k * L >= 4:
+            shards = rm.send_shards(rng.randbytes(k * L - 4), n, variant)[0]
+        else:
+            shards = np.zeros((n, L), dtype=np.uint8)
+            shards[:k] = np.frombuffer(rng.randbytes(k * L), dtype=np.uint8).reshape(k, L)
+            if m:
+                shards = rm.ReedSolomon(k, m).encode(shards)
+        assert shards.shape == (n, L)
+        leaves, tree = _tree(shards, variant)
+        bad = shards.copy()
+        bad[0, 0] ^= 0x5A
+        bad_leaves, bad_tree = _tree(bad, variant)
+        for pattern in FORM_PATTERNS:
+            present = np.ones(n, dtype=np.uint8)
+            root, lv = tree.root_hash(), leaves
+            if pattern == "one data shard missing":
+                present[0] = 0
+            elif pattern == "k - 1 present":
+                present[k - 1:] = 0
+            elif pattern == "tampered tree":
+                present[0] = 0
+                root, lv = bad_tree.root_hash(), bad_leaves
+            elif pattern == "wrong root":
+                root, lv = bytes([root[0] ^ 1]) + root[1:], None
+            cases.append((L, pattern, shards, present, root, lv, bad_tree if pattern == "tampered tree" else tree))
+    return cases
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("k,m", [(2, 2), (3, 2), (1, 0)])
+def test_decode_forms_agree(hbx_ctx, k, m, variant):
+    """hbx_broadcast_decode_leaves_d (one call per shard length), hbx_broadcast_decode_ragged_d with
+    and without leaf digests (all lengths in one call) and hbx_broadcast_decode_insts out of an echo
+    store give the same status, out_len and payload on the same shards, and the oracle's payload where
+    the oracle decodes."""
+    assert rm.coding_counts(k + m) == (k, m)
+    n = k + m
+    _set_merkle(hbx_ctx, variant)
+    cases = _form_cases(k, m, variant)
+    got = {}  # form -> [(status, out_len, payload)] in the order of `cases`
+
+    def results(st, ln, out, out_off):
+        st, ln, out = st.cpu().numpy(), ln.cpu().numpy(), out.cpu().numpy().reshape(-1)
+        return [(int(s), int(v), out[int(o): int(o) + int(v)].tobytes() if s == 0 else None)
+                for s, v, o in zip(st, ln, out_off)]
+
+    def digests(case):
+        L, _, shards, present, _, _, _ = case
+        return np.stack([np.frombuffer(rm.hash_leaf(bytes([i]) + shards[i].tobytes(), variant), dtype=np.uint8)
+                         if present[i] else np.zeros(32, dtype=np.uint8) for i in range(n)])
+
+    def held(case):  # the rows a receiver holds: withheld shards are zero bytes
+        return case[2] * case[3][:, None]
+
+    # uniform rows, leaf digests given: one call per length
+    got["leaves_d"] = []
+    for L in FORM_LENS:
+        sel = [c for c in cases if c[0] == L]
+        stride = max(k * L - 4, 0) + 16
+        d_out = torch.zeros((len(sel), stride), dtype=torch.uint8, device="cuda")
+        d_len = torch.zeros(len(sel), dtype=torch.int64, device="cuda")
+        d_st = torch.zeros(len(sel), dtype=torch.int32, device="cuda")
+        hbx_ctx.broadcast_decode_leaves_d(dev(np.stack([held(c) for c in sel])), dev(np.stack([c[3] for c in sel])),
+                                          dev(np.stack([digests(c) for c in sel])),
+                                          dev(np.stack([np.frombuffer(c[4], dtype=np.uint8) for c in sel])), k, m,
+                                          d_out, d_len, d_st)
+        torch.cuda.synchronize()
+        got["leaves_d"] += results(d_st, d_len, d_out, [r * stride for r in range(len(sel))])
+    # ragged rows, with and without leaf digests: every length in one call
+    lens = np.array([c[0] for c in cases], dtype=np.uint32)
+    off, pitch, total = hbx.ragged_layout(lens, n)
+    buf = np.zeros(total, dtype=np.uint8)
+    for r, c in enumerate(cases):
+        buf[int(off[r]): int(off[r]) + n * int(pitch[r])].reshape(n, int(pitch[r]))[:, : c[0]] = held(c)
+    room = (np.maximum(k * lens.astype(np.int64) - 4, 0) + 15) // 16 * 16
+    out_off = np.concatenate(([0], np.cumsum(room)[:-1])).astype(np.uint64)
+    present = dev(np.stack([c[3] for c in cases]))
+    roots = np.stack([np.frombuffer(c[4], dtype=np.uint8) for c in cases])
+    for form, leaf in (("ragged_d", None), ("ragged_d leaves", dev(np.stack([digests(c) for c in cases])))):
+        d_out = torch.zeros(max(int(room.sum()), 16), dtype=torch.uint8, device="cuda")
+        d_len = torch.zeros(len(cases), dtype=torch.int64, device="cuda")
+        d_st = torch.zeros(len(cases), dtype=torch.int32, device="cuda")
+        hbx_ctx.broadcast_decode_ragged_d(dev(buf), off, lens, pitch, present, dev(roots), k, m, d_out, out_off, d_len,
+                                          d_st, d_leaf_hash=leaf)
+        torch.cuda.synchronize()
+        got[form] = results(d_st, d_len, d_out, out_off)
+    # the echo store: one instance per case, the present shards' proofs added, one attempt per case
+    stored = [r for r, c in enumerate(cases) if c[5] is not None]
+    hbx_ctx.prepare_broadcast(len(cases), k, m, max(FORM_LENS))
+    items = [(cases[r][6].gen_proof(cases[r][5][i]), r, i) for r in stored for i in range(n) if cases[r][3][i]]
+    if items:
+        assert _add(hbx_ctx, items).tolist() == [STORED] * len(items)
+    vals, status = hbx_ctx.broadcast_decode_insts(stored, roots[stored], lens[stored])
+    # equal across the forms, and the oracle's payload where the oracle decodes
+    for r, (L, pattern, shards, pres, root, lv, _) in enumerate(cases):
+        what = (L, pattern)
+        assert got["leaves_d"][r] == got["ragged_d"][r] == got["ragged_d leaves"][r], what
+        st, ln, payload = got["ragged_d"][r]
+        if r in stored:
+            a = stored.index(r)
+            assert (int(status[a]), vals[a]) == (st, payload), what
+        leaf_values = [bytes([i]) + shards[i].tobytes() if pres[i] else None for i in range(n)]
+        want = ob.decode_from_shards(leaf_values, n, root, variant)
+        if want is not None:
+            assert st == 0 and payload == want and ln == len(want), what
+        elif k * L >= 4:  # the oracle's None is a decode error, not a payload too short for its header
+            assert st != 0, what
+    by = {(c[0], c[1]): got["ragged_d"][r][0] for r, c in enumerate(cases)}
+    assert by[(8, "all present")] == 0 and by[(5, "all present")] == 0
+    assert by[(8, "wrong root")] == hbx.HBX_E_ROOT_MISMATCH
+    if m:
+        assert by[(8, "k - 1 present")] == hbx.HBX_E_TOO_FEW_SHARDS
+        assert by[(8, "tampered tree")] == hbx.HBX_E_ROOT_MISMATCH
+        assert by[(8, "one data shard missing")] == 0
